@@ -6,6 +6,14 @@ with the fraction of the HBM3E read roofline.  One "step" = one
 lnx_crc32_batch call over the rank's whole frame batch (inputs already in HBM).
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--op OP]
+                  [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps, writes its outputs when
+--dump-outputs is given and prints the result line.  --full adds the
+measurements that take runs of their own: "slice16m" and "cpu_baseline" below.
+--dump-outputs DIR writes what the last timed step computed (the arrays a
+caller of the timed entry receives) as DIR/<name>.npy; the inputs are the same
+from run to run, so two builds can be compared output for output.
 
 --op crc32 (default, the BASELINE metric) | fcs_append (lnx_fcs_append_batch: TX FCS
 append in place on 1496-B frames in 1536-B ring slots, lengths reset each step) | tx_finish (lnx_tx_finish_batch:
@@ -15,9 +23,9 @@ every frame as one segment, random pseudo-header seeds) | ingress
 (lnx_ingress_verify_batch: the frames get Ethernet/IPv4/UDP headers written in
 place, so every frame takes the full header-sum + UDP-sum path).
 
-N=1 runs BASELINE configs[1] (1 M x 1500 B) and, beside `value`, a "slice16m"
-sub-measurement: the same kernel over 16 M x 1500 B, the per-GPU slice the
-N>1 runs use, so the driver's scaling series has an equal-work N=1 point.  For
+N=1 runs BASELINE configs[1] (1 M x 1500 B) and, with --full, beside `value` a
+"slice16m" sub-measurement: the same kernel over 16 M x 1500 B, the per-GPU slice
+the N>1 runs use, so the driver's scaling series has an equal-work N=1 point.  For
 N>1 (launched by torch.distributed.run, one rank per GPU) every rank owns its
 own contiguous slice of configs[4] (128 M x 1500 B over 8 GPUs = 16 M frames
 per GPU); frames are partitioned by index with no data-path collective (weak
@@ -25,8 +33,9 @@ scaling).  The barrier / MAX-over-ranks timing runs over a gloo process group
 (host-side clock only): the path needs no RCCL, so none is initialised.
 
 Rank 0 prints ONE JSON line.  Extra fields: "roofline" (dominant kernel,
-HIP-event timed on its launch stream), "cpu_baseline" (the C oracle on the
-box's host cores, bounded sample, N=1 only).
+HIP-event timed on its launch stream, inside the K timed steps) and, with
+--full, "cpu_baseline" (the C oracle on the box's host cores, bounded sample,
+N=1 only).
 """
 from __future__ import annotations
 
@@ -41,7 +50,9 @@ import numpy as np
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
-HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak, /opt/skills/guides/MI355X_MICROARCH.md
+HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak
+DUMP_BUDGET_BYTES = 48 << 20  # --dump-outputs: all files together (under the 64 MB a dump may take)
+DUMP_SEED = 0x6c6e78
 FRAME_BYTES = 1500
 
 
@@ -165,6 +176,42 @@ def cpu_baseline(d_bytes, off_np, frame_len, budget_s: float = 10.0, threads: in
     return out
 
 
+def dump_outputs(dirname: str, arrays: dict, rank: int = 0) -> dict:
+    """--dump-outputs: every array of `arrays` (name -> numpy array or torch
+    tensor, integer results of the timed entry) as DIR/<name>.npy (ranks past 0:
+    <name>.rank<r>.npy).  32-bit results are stored as float64 and narrower ones as
+    float32, both exact.  An array over its share of DUMP_BUDGET_BYTES is
+    sampled: the elements at a fixed, seeded, sorted list of flat indices (drawn
+    with replacement; the same for every run with the same arguments).  Returns
+    what was written."""
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // max(1, len(arrays))
+    written = {}
+    for k, (name, a) in enumerate(sorted(arrays.items())):
+        wide = a.dtype.itemsize > 2 if isinstance(a, np.ndarray) else a.element_size() > 2
+        ftype = np.float64 if wide else np.float32
+        cap = share // np.dtype(ftype).itemsize
+        n = int(a.size if isinstance(a, np.ndarray) else a.numel())
+        sampled = n > cap
+        if sampled:
+            idx = np.sort(np.random.default_rng(DUMP_SEED + k).integers(0, n, cap))
+            if isinstance(a, np.ndarray):
+                a = a.reshape(-1)[idx]
+            else:
+                import torch
+                a = a.reshape(-1)[torch.from_numpy(idx).to(a.device)]
+        if not isinstance(a, np.ndarray):
+            a = a.cpu().numpy()
+        if a.dtype == np.int32:
+            a = a.view(np.uint32)  # CRCs travel in int32 tensors
+        elif a.dtype == np.int16:
+            a = a.view(np.uint16)
+        fname = f"{name}.npy" if rank == 0 else f"{name}.rank{rank}.npy"
+        np.save(os.path.join(dirname, fname), a.astype(ftype))
+        written[fname] = {"elements": int(a.size), "of": n, "dtype": np.dtype(ftype).name, "sampled": sampled}
+    return written
+
+
 def rx_ring_bench(args, L, synth, torch, dev, world):
     """PCIe-inclusive receive path: frames
     (incl. their LE FCS) sit in the ring's pinned host slots as a NIC would
@@ -210,8 +257,10 @@ def rx_ring_bench(args, L, synth, torch, dev, world):
         assert ok.all(), "FCS verify failed on valid frames"
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            ring.ingress(0, n)
+            ok, verdict = ring.ingress(0, n)
         el = (time.perf_counter() - t0) / args.steps
+        dumped = dump_outputs(args.dump_outputs, {"fcs_ok": np.asarray(ok), "verdict": np.asarray(verdict)}) \
+            if args.dump_outputs else None
     finally:
         ring.close()
     nbytes = int(off_np[-1])
@@ -236,6 +285,8 @@ def rx_ring_bench(args, L, synth, torch, dev, world):
                    "pcie_bytes_per_frame_byte": round(h2d / nbytes, 4),
                    "depth": args.ring_depth, "batch_slots": args.ring_batch, "kernel": L.version()},
     }
+    if dumped:
+        out["dumped_outputs"] = dumped
     print(json.dumps(out), flush=True)
 
 
@@ -374,6 +425,14 @@ def packets_bench(args, L, synth, torch, dev, world):
         for _ in range(args.steps):
             step()
         el = (time.perf_counter() - t0) / args.steps
+        dumped = None
+        if args.dump_outputs:
+            res = {"status": status, "lens": lens}
+            if args.op == "egress_packets":
+                res["frames"] = np.asarray(rows)  # finished in place (a sample of the slots)
+            else:
+                res["verdict"] = verdict
+            dumped = dump_outputs(args.dump_outputs, res)
     finally:
         ring.close()
     nbytes = int(wire.sum())
@@ -389,6 +448,8 @@ def packets_bench(args, L, synth, torch, dev, world):
                    "mpps": round(n / el / 1e6, 2), "depth": args.ring_depth, "batch_slots": args.ring_batch,
                    "kernel": L.version()},
     }
+    if dumped:
+        out["dumped_outputs"] = dumped
     print(json.dumps(out), flush=True)
 
 
@@ -438,12 +499,20 @@ def main():
                     help="--op *_packets: pageable buffers of the caller, or views of the ring's slots")
     ap.add_argument("--prewarm-s", type=float, default=0.5,
                     help="untimed launches for this long before the W warmup steps (GPU clock ramp)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-slice16m", action="store_true", help="skip the 16 M-frame equal-work sub-measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="also the measurements that take runs of their own: the 16 M-frame equal-work "
+                         "sub-measurement (slice16m) and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-slice16m", action="store_true",
+                    help="--full without the 16 M-frame equal-work sub-measurement")
     ap.add_argument("--cpu-budget", type=float, default=10.0)
     ap.add_argument("--with-copies", action="store_true", help="also time pinned H2D+kernel+D2H")
     ap.add_argument("--verify", action="store_true", help="spot-check results against the oracle")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     import torch
     import lneto_amd as L
@@ -511,7 +580,8 @@ def main():
     if args.op == "sum16":
         d_seg = d_off[:-1].contiguous()
         d_len = (d_off[1:] - d_off[:-1]).to(torch.int32)
-        d_seed = torch.randint(0, 1 << 20, (n_local,), dtype=torch.int32, device=dev)
+        d_seed = torch.randint(0, 1 << 20, (n_local,), dtype=torch.int32, device=dev,
+                               generator=torch.Generator(device=dev).manual_seed(synth.SEED + rank))
         d_sum = torch.empty(n_local, dtype=torch.int16, device=dev)
     elif args.op == "fcs_verify":
         d_ok = torch.empty(n_local, dtype=torch.uint8, device=dev)
@@ -855,7 +925,26 @@ def main():
             assert int(got[i]) == want, f"mismatch frame {i}"
         out["verified_sample"] = len(idx)
 
-    if world == 1 and args.op == "crc32" and wname == "mtu1500" and not cpu_ranks and not args.no_slice16m:
+    if args.dump_outputs:
+        # what a caller of the timed entry holds after the last step
+        if args.op == "sum16":
+            res = {"sum16": d_sum}
+        elif args.op in ("fcs_verify", "ingress", "pcap"):
+            res = {"ok": d_ok}
+        elif args.op == "rx_verify":
+            res = {"fcs_ok": d_ok, "verdict": d_verdict}
+        elif args.op == "tx_checksum":
+            res = {"status": d_ok, "frames": d_bytes}
+        elif args.op == "search":
+            res = {"hit": d_hit}
+        elif args.op in ("fcs_append", "tx_finish"):
+            res = {"status": d_status, "lens": d_len, "frames": d_bytes}
+        else:
+            res = {"crc32": d_crc}
+        out["dumped_outputs"] = dump_outputs(args.dump_outputs, res, rank)
+
+    if (args.full and world == 1 and args.op == "crc32" and wname == "mtu1500" and not cpu_ranks
+            and not args.no_slice16m):
         out["slice16m"] = slice16m_bench(L, synth, torch, dev)
 
     if args.with_copies and rank == 0:
@@ -875,8 +964,8 @@ def main():
         out["pcie_inclusive"] = {"value": round(nbytes / el / 2**30, 2), "unit": "GiB/s",
                                  "note": "pinned H2D of frames + kernel + D2H of CRCs, serial, 1 stream"}
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.op not in ("fcs_append", "tx_checksum",
-                                                                                  "tx_finish"):
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.op not in (
+            "fcs_append", "tx_checksum", "tx_finish"):
         out["cpu_baseline"] = cpu_baseline(d_bytes, off_np, flen, budget_s=args.cpu_budget, op=args.op)
 
     if rank == 0:

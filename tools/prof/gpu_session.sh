@@ -8,7 +8,7 @@
 # Steps:
 #   tests[:EXPR]      pytest -m gpu (optionally -k EXPR; "_or_" stands for " or ")
 #   smoke             __graft_entry__.smoke()
-#   bench             the default bench line (what the driver runs)
+#   bench             the default bench line with --full (slice16m and the CPU baseline beside it)
 #   lines             a --verify'd bench line per workload / op
 #   line:WL:OP[:ARGS] one bench line (ARGS: extra flags, comma-separated)
 #   prof:WL[:OP[:short]] rocprofv3 kernel trace + PMC passes (tools/prof/profile.sh)
@@ -37,9 +37,9 @@ for STEP in "$@"; do
       fi
       tail -3 $O/gpu_tests.log ;;
     smoke) run 120 $O/smoke.log python -u -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) run 240 $O/bench_default.jsonl python -u bench.py --steps 20 --warmup 5; tail -1 $O/bench_default.jsonl ;;
+    bench) run 240 $O/bench_default.jsonl python -u bench.py --full --steps 20 --warmup 5; tail -1 $O/bench_default.jsonl ;;
     lines)
-      run 240 $O/bench_mtu1500.jsonl python -u bench.py --verify
+      run 240 $O/bench_mtu1500.jsonl python -u bench.py --full --verify
       for WL in jumbo9000 zipf64_1500; do
         run 240 $O/bench_$WL.jsonl python -u bench.py --workload $WL --no-cpu-baseline --verify
       done
