@@ -57,6 +57,14 @@ uint32_t lnx_crc32_update(uint32_t crc, const uint8_t* p, size_t n);
 /* Go: ethernet.CRC32(data) (ethernet/crc.go:19-21). CRC32(nil) == 0. */
 uint32_t lnx_crc32(const uint8_t* p, size_t n);
 
+/* CRC32(A || B) from CRC32(A), CRC32(B) and len(B), exact for every 64-bit
+ * length (zlib's crc32_combine):
+ *   lnx_crc32_combine(lnx_crc32(A), lnx_crc32(B), |B|) == lnx_crc32(A || B),
+ *   lnx_crc32_combine(seed, lnx_crc32(B), |B|) == lnx_crc32_update(seed, B).
+ * Joins CRCs taken over pieces of a frame, in other launches or on other
+ * devices; associative, identity (crc 0, length 0). */
+uint32_t lnx_crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b);
+
 /* Go: ethernet.CRC32Search(data, minOffCRC) (ethernet/crc.go:28-47).
  * First off >= max(minOff,0) with CRC32(data[:off]) == LE32(data[off:]),
  * or -1. */
@@ -133,8 +141,8 @@ int lnx_fcs_append(uint8_t* frame, uint32_t* len, uint32_t capacity);
  * alignment.  Each workgroup slice's kernel is picked on the device from its
  * offsets, so the call never reads device memory on the host
  * and never syncs.  Replaces n calls of
- * ethernet.CRC32 (ethernet/crc.go:19-21) / of the CRC32Update hook with crc=0
- * (internet/stack-ethernet.go:211-214). */
+ * ethernet.CRC32 (ethernet/crc.go:19-21) / of the CRC32Update hook
+ * (internet/stack-ethernet.go:211-214; its crc argument: lnx_crc32_update_batch). */
 int lnx_crc32_batch(const uint8_t* d_bytes, const uint64_t* d_off, uint64_t n,
                     uint32_t* d_crc, void* stream);
 
@@ -157,6 +165,58 @@ int lnx_fcs_verify_batch_ex(const uint8_t* d_bytes, const uint64_t* d_off, uint6
  * from its own start. */
 int lnx_crc32_segments(const uint8_t* d_bytes, const uint64_t* d_start, const uint32_t* d_len, uint64_t n,
                        uint32_t* d_crc, void* stream);
+
+/* ---- running CRCs: seeds, combine, frames made of segments ----
+ * As every batch entry these are asynchronous on `stream`, never sync, never
+ * read device memory on the host, never allocate and retain nothing (hence the
+ * caller's workspace below).  A zero count (n, nframes) returns LNX_OK; a NULL
+ * required pointer with a non-zero count LNX_EINVAL; no usable device
+ * LNX_ENODEV / LNX_EHIP. */
+
+/* d_out[i] = lnx_crc32_combine(d_crc_a[i], d_crc_b[i], d_len_b[i]) for i in
+ * [0, n).  d_out may alias d_crc_a or d_crc_b. */
+int lnx_crc32_combine_batch(const uint32_t* d_crc_a, const uint32_t* d_crc_b, const uint64_t* d_len_b, uint64_t n,
+                            uint32_t* d_out, void* stream);
+
+/* The CRC32Update hook with its crc argument (internet/stack-ethernet.go:31-32):
+ * d_crc[i] = CRC32Update(d_seed[i], d_bytes[d_off[i] : d_off[i+1]]), offsets as
+ * lnx_crc32_batch (an end offset below its start is an empty frame: its result
+ * is the seed itself).  d_seed NULL = all-zero seeds, then identical to
+ * lnx_crc32_batch (and no further launch); else lnx_crc32_batch's launches
+ * into d_crc and one launch that folds the seeds in.  d_seed and d_crc must
+ * not overlap: the host compares the two address ranges and returns LNX_EINVAL
+ * if they do.  A running CRC over several calls (data that arrives in pieces)
+ * ping-pongs two arrays: call k reads the array call k-1 wrote and writes the
+ * other. */
+int lnx_crc32_update_batch(const uint8_t* d_bytes, const uint64_t* d_off, uint64_t n, const uint32_t* d_seed,
+                           uint32_t* d_crc, void* stream);
+
+/* Frames made of segments (a jumbo frame in several ring slots, a header
+ * buffer plus a payload buffer): frame f is the concatenation, in index order,
+ * of segments d_first[f] .. d_first[f+1]-1; segment k is
+ * d_bytes[d_start[k] : d_start[k] + d_len[k]].
+ *   d_crc[f] = CRC32Update(d_seed ? d_seed[f] : 0, frame f).
+ * Segments may lie in any address order, overlap (as lnx_crc32_segments) and
+ * be empty.  A frame with d_first[f+1] <= d_first[f] has no segments: its CRC
+ * is its seed (0 without one).  d_first holds nframes+1 entries and the caller
+ * keeps d_first[nframes] <= nseg; the kernel still clamps every segment index
+ * to nseg, so no d_first makes it read past the segment arrays.  d_seg_crc is
+ * the caller's workspace of nseg uint32 (not overlapping d_crc), left holding
+ * each segment's own CRC (what lnx_crc32_segments gives).  nseg == 0 with
+ * nframes > 0 is valid (every frame empty); d_bytes, d_start, d_len and
+ * d_seg_crc may then be NULL.  Two launches: lnx_crc32_segments' into
+ * d_seg_crc, then the fold of each frame's (CRC, length) pairs. */
+int lnx_crc32_chain_batch(const uint8_t* d_bytes, const uint64_t* d_start, const uint32_t* d_len, uint64_t nseg,
+                          const uint64_t* d_first, uint64_t nframes, const uint32_t* d_seed, uint32_t* d_seg_crc,
+                          uint32_t* d_crc, void* stream);
+
+/* FCS verify of frames made of segments (arguments as lnx_crc32_chain_batch):
+ * d_ok[f] = 1 iff frame f's total length >= 4 and its CRC (seed 0) is
+ * LNX_CRC32_RESIDUE, wherever the 4 FCS bytes fall (also across a segment
+ * boundary); a frame with no segments gives 0.  One byte per frame. */
+int lnx_fcs_verify_chain_batch(const uint8_t* d_bytes, const uint64_t* d_start, const uint32_t* d_len, uint64_t nseg,
+                               const uint64_t* d_first, uint64_t nframes, uint32_t* d_seg_crc, uint8_t* d_ok,
+                               void* stream);
 
 /* Batched TX FCS append: the tail of
  * StackEthernet.Encapsulate with the CRC32Update hook set

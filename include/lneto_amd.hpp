@@ -82,6 +82,9 @@ inline uint32_t CRC32Update(uint32_t crc, const uint8_t* p, size_t n) { return l
 
 inline uint32_t CRC32(Bytes data) { return lnx_crc32(data.p, data.n); }
 
+// CRC32(A || B) from CRC32(A), CRC32(B) and len(B); CRC32Combine(seed, CRC32(B), len(B)) == CRC32Update(seed, B).
+inline uint32_t CRC32Combine(uint32_t crcA, uint32_t crcB, uint64_t lenB) { return lnx_crc32_combine(crcA, crcB, lenB); }
+
 inline int CRC32Search(Bytes data, int minOffCRC) {
   return (int)lnx_crc32_search(data.p, data.n, minOffCRC);
 }
@@ -102,6 +105,26 @@ inline int VerifyFCSBatch(const uint8_t* d_frames, const uint64_t* d_off, uint64
 inline int CRC32Segments(const uint8_t* d_bytes, const uint64_t* d_start, const uint32_t* d_len, uint64_t n,
                          uint32_t* d_crc, void* stream = nullptr) {
   return lnx_crc32_segments(d_bytes, d_start, d_len, n, d_crc, stream);
+}
+// Running CRCs (device pointers): CRC32Combine per pair; the CRC32Update hook with a seed per frame
+// (d_seed and d_crc must not overlap); frames made of segments, and their FCS check.
+inline int CRC32CombineBatch(const uint32_t* d_crcA, const uint32_t* d_crcB, const uint64_t* d_lenB, uint64_t n,
+                             uint32_t* d_out, void* stream = nullptr) {
+  return lnx_crc32_combine_batch(d_crcA, d_crcB, d_lenB, n, d_out, stream);
+}
+inline int CRC32UpdateBatch(const uint8_t* d_frames, const uint64_t* d_off, uint64_t n, const uint32_t* d_seed,
+                            uint32_t* d_crc, void* stream = nullptr) {
+  return lnx_crc32_update_batch(d_frames, d_off, n, d_seed, d_crc, stream);
+}
+inline int CRC32ChainBatch(const uint8_t* d_bytes, const uint64_t* d_start, const uint32_t* d_len, uint64_t nseg,
+                           const uint64_t* d_first, uint64_t nframes, const uint32_t* d_seed, uint32_t* d_segCRC,
+                           uint32_t* d_crc, void* stream = nullptr) {
+  return lnx_crc32_chain_batch(d_bytes, d_start, d_len, nseg, d_first, nframes, d_seed, d_segCRC, d_crc, stream);
+}
+inline int VerifyFCSChainBatch(const uint8_t* d_bytes, const uint64_t* d_start, const uint32_t* d_len, uint64_t nseg,
+                               const uint64_t* d_first, uint64_t nframes, uint32_t* d_segCRC, uint8_t* d_ok,
+                               void* stream = nullptr) {
+  return lnx_fcs_verify_chain_batch(d_bytes, d_start, d_len, nseg, d_first, nframes, d_segCRC, d_ok, stream);
 }
 // CRC32Search over every capture bytes[off[i] : off[i+1]] (ethernet/crc.go:28-47).
 inline int CRC32SearchBatch(const uint8_t* d_bytes, const uint64_t* d_off, const int64_t* d_minOffCRC, uint64_t n,

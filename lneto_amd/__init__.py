@@ -21,6 +21,7 @@ import os
 __all__ = [
     "LnetoError", "lib", "crc32", "crc32_update", "crc32_search", "sum_write_even", "sum16",
     "payload_sum16", "never_zero_sum", "CRC791", "crc32_batch", "fcs_verify_batch", "sum16_batch",
+    "crc32_combine", "crc32_combine_batch", "crc32_update_batch", "crc32_chain_batch", "fcs_verify_chain_batch",
     "crc32_batch_host", "crc32_batch_multi", "tx_checksum_batch", "rx_verify_batch", "device_count", "version", "build_id", "LIB_PATH",
     "CRC32_RESIDUE", "RxRing", "RxFilter", "RX_NO_FCS", "research_lib",
 ]
@@ -98,6 +99,11 @@ class RxFilter(ctypes.Structure):
 _sig = {
     "lnx_crc32_update": (ctypes.c_uint32, [ctypes.c_uint32, _u8p, ctypes.c_size_t]),
     "lnx_crc32": (ctypes.c_uint32, [_u8p, ctypes.c_size_t]),
+    "lnx_crc32_combine": (ctypes.c_uint32, [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64]),
+    "lnx_crc32_combine_batch": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_uint64, _vp, _vp]),
+    "lnx_crc32_update_batch": (ctypes.c_int, [_vp, _vp, ctypes.c_uint64, _vp, _vp, _vp]),
+    "lnx_crc32_chain_batch": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_uint64, _vp, ctypes.c_uint64, _vp, _vp, _vp, _vp]),
+    "lnx_fcs_verify_chain_batch": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_uint64, _vp, ctypes.c_uint64, _vp, _vp, _vp]),
     "lnx_crc32_search": (ctypes.c_int64, [_u8p, ctypes.c_size_t, ctypes.c_int64]),
     "lnx_sum_write_even": (ctypes.c_uint32, [ctypes.c_uint32, _u8p, ctypes.c_size_t]),
     "lnx_sum16": (ctypes.c_uint16, [ctypes.c_uint32]),
@@ -172,6 +178,14 @@ def crc32(p: bytes) -> int:
     """ethernet.CRC32 (ethernet/crc.go:19-21)."""
     b, n = _buf(p)
     return lib.lnx_crc32(b, n)
+
+
+def crc32_combine(crc_a: int, crc_b: int, len_b: int) -> int:
+    """CRC32(A || B) from CRC32(A), CRC32(B) and len(B) (lnx_crc32_combine; zlib's crc32_combine).
+    crc32_combine(seed, crc32(B), len(B)) == crc32_update(seed, B)."""
+    if not 0 <= len_b < 2**64:
+        raise LnetoError("crc32_combine: len_b must be in [0, 2**64)")
+    return lib.lnx_crc32_combine(crc_a & 0xFFFFFFFF, crc_b & 0xFFFFFFFF, len_b)
 
 
 def crc32_search(p: bytes, min_off: int) -> int:
@@ -365,6 +379,97 @@ def crc32_segments(d_bytes, d_start, d_len, out=None, stream=None):
         with b as s:
             _check(lib.lnx_crc32_segments(d_bytes.data_ptr(), d_start.data_ptr(), d_len.data_ptr(), n,
                                           out.data_ptr(), s), what)
+    return out
+
+
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
+def crc32_combine_batch(d_crc_a, d_crc_b, d_len_b, out=None, stream=None):
+    """out[i] = crc32_combine(d_crc_a[i], d_crc_b[i], d_len_b[i]) on the GPU
+    (lnx_crc32_combine_batch).  d_crc_a, d_crc_b: int32 (N, uint32 bits); d_len_b:
+    int64 (N).  ``out`` may be d_crc_a or d_crc_b.  Returns int32 (N)."""
+    import torch
+    what = "lnx_crc32_combine_batch"
+    b = _Batch(what, [("d_crc_a", d_crc_a, "i32"), ("d_crc_b", d_crc_b, "i32"), ("d_len_b", d_len_b, "i64")], stream)
+    n = d_crc_a.numel()
+    _need_len(what, "d_crc_b", d_crc_b, n)
+    _need_len(what, "d_len_b", d_len_b, n)
+    out = _out(what, out, n, torch.int32, "i32", b.device)
+    if n > 0:
+        with b as s:
+            _check(lib.lnx_crc32_combine_batch(d_crc_a.data_ptr(), d_crc_b.data_ptr(), d_len_b.data_ptr(), n,
+                                               out.data_ptr(), s), what)
+    return out
+
+
+def crc32_update_batch(d_bytes, d_off, d_seed=None, out=None, stream=None):
+    """The CRC32Update hook with its crc argument, batched (lnx_crc32_update_batch):
+    out[i] = crc32_update(d_seed[i], d_bytes[d_off[i]:d_off[i+1]]).  d_seed: int32
+    (N) or None (all zero: crc32_batch).  ``out`` must not overlap d_seed; a
+    running CRC over several calls ping-pongs two arrays.  Returns int32 (N)."""
+    import torch
+    what = "lnx_crc32_update_batch"
+    b = _Batch(what, [("d_bytes", d_bytes, "u8"), ("d_off", d_off, "i64"), ("d_seed", d_seed, "i32?")], stream)
+    n = d_off.numel() - 1
+    _need_len(what, "d_seed", d_seed, n)
+    out = _out(what, out, n, torch.int32, "i32", b.device)
+    if n > 0:
+        with b as s:
+            _check(lib.lnx_crc32_update_batch(d_bytes.data_ptr(), d_off.data_ptr(), n, _ptr(d_seed), out.data_ptr(), s),
+                   what)
+    return out
+
+
+def _chain_args(what, d_bytes, d_start, d_len, d_first, d_seed, seg_crc, nseg, stream):
+    import torch
+    b = _Batch(what, [("d_bytes", d_bytes, "u8"), ("d_start", d_start, "i64"), ("d_len", d_len, "i32"),
+                      ("d_first", d_first, "i64"), ("d_seed", d_seed, "i32?")], stream)
+    nframes = d_first.numel() - 1
+    if nseg is None:
+        nseg = d_start.numel()
+    _need_len(what, "d_start", d_start, nseg)
+    _need_len(what, "d_len", d_len, nseg)
+    _need_len(what, "d_seed", d_seed, nframes)
+    # the library allocates nothing: the workspace is made here when the caller passes none
+    seg_crc = _out(what, seg_crc, nseg, torch.int32, "i32", b.device)
+    return b, nseg, nframes, seg_crc
+
+
+def crc32_chain_batch(d_bytes, d_start, d_len, d_first, d_seed=None, out=None, seg_crc=None, nseg=None, stream=None):
+    """CRC32 of frames made of segments (lnx_crc32_chain_batch): frame f is the
+    concatenation of segments d_first[f] .. d_first[f+1]-1, segment k is
+    d_bytes[d_start[k] : d_start[k] + d_len[k]] (int64 starts, int32 lengths,
+    int64 d_first of nframes+1 entries); out[f] = crc32_update(d_seed[f] or 0,
+    frame f).  ``seg_crc`` (int32, nseg) is the workspace, allocated when None
+    and left holding each segment's own CRC; ``nseg`` (default: all of d_start)
+    counts the segments in use.  Returns int32 (nframes)."""
+    import torch
+    what = "lnx_crc32_chain_batch"
+    b, nseg, nframes, seg_crc = _chain_args(what, d_bytes, d_start, d_len, d_first, d_seed, seg_crc, nseg, stream)
+    out = _out(what, out, nframes, torch.int32, "i32", b.device)
+    if nframes > 0:
+        with b as s:
+            _check(lib.lnx_crc32_chain_batch(d_bytes.data_ptr(), d_start.data_ptr(), d_len.data_ptr(), nseg,
+                                             d_first.data_ptr(), nframes, _ptr(d_seed), seg_crc.data_ptr(),
+                                             out.data_ptr(), s), what)
+    return out
+
+
+def fcs_verify_chain_batch(d_bytes, d_start, d_len, d_first, out=None, seg_crc=None, nseg=None, stream=None):
+    """1 where frame f (segments as crc32_chain_batch, trailing LE FCS included,
+    wherever its 4 bytes fall) passes the FCS check, else 0
+    (lnx_fcs_verify_chain_batch).  Returns uint8 (nframes)."""
+    import torch
+    what = "lnx_fcs_verify_chain_batch"
+    b, nseg, nframes, seg_crc = _chain_args(what, d_bytes, d_start, d_len, d_first, None, seg_crc, nseg, stream)
+    out = _out(what, out, nframes, torch.uint8, "u8", b.device)
+    if nframes > 0:
+        with b as s:
+            _check(lib.lnx_fcs_verify_chain_batch(d_bytes.data_ptr(), d_start.data_ptr(), d_len.data_ptr(), nseg,
+                                                  d_first.data_ptr(), nframes, seg_crc.data_ptr(), out.data_ptr(), s),
+                   what)
     return out
 
 

@@ -15,6 +15,17 @@
 #include "rx_filter.hpp"
 #include "dispatch.hpp"
 
+// crc32_combine_kernel.hip: the running-crc forms
+namespace lnxc {
+hipError_t launch_combine_pairs(const uint32_t* a, const uint32_t* b, const uint64_t* len, uint64_t n, uint32_t* out,
+                                int num_cus, hipStream_t stream);
+hipError_t launch_seed_pairs(const uint32_t* seed, const uint64_t* off, uint64_t n, uint32_t* crc, int num_cus,
+                             hipStream_t stream);
+hipError_t launch_chain_fold(const uint32_t* seg_crc, const uint32_t* len, uint64_t nseg, const uint64_t* first,
+                             uint64_t nframes, const uint32_t* seed, void* out, bool verify, int num_cus,
+                             hipStream_t stream);
+}  // namespace lnxc
+
 namespace lnx {
 hipError_t launch_crc32_frames(const uint8_t* bytes, const uint64_t* off, uint64_t n, void* out,
                                bool verify, const void* image, int num_cus, hipStream_t stream, uint32_t policy,
@@ -564,6 +575,70 @@ int lnx_crc32_segments(const uint8_t* d_bytes, const uint64_t* d_start, const ui
   return LNX_OK;
 }
 
+int lnx_crc32_combine_batch(const uint32_t* d_crc_a, const uint32_t* d_crc_b, const uint64_t* d_len_b, uint64_t n,
+                            uint32_t* d_out, void* stream) {
+  if (n == 0) return LNX_OK;
+  if (!d_crc_a || !d_crc_b || !d_len_b || !d_out) return LNX_EINVAL;
+  DeviceCtx* c = nullptr;
+  int st = get_ctx(&c);
+  if (st != LNX_OK) return st;
+  const hipError_t e = lnxc::launch_combine_pairs(d_crc_a, d_crc_b, d_len_b, n, d_out, c->num_cus,
+                                                  static_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return hip_fail(e, "combine_pairs_kernel launch");
+  return LNX_OK;
+}
+
+int lnx_crc32_update_batch(const uint8_t* d_bytes, const uint64_t* d_off, uint64_t n, const uint32_t* d_seed,
+                           uint32_t* d_crc, void* stream) {
+  if (n == 0) return LNX_OK;
+  if (!d_bytes || !d_off || !d_crc) return LNX_EINVAL;
+  if (d_seed) {
+    // the second launch reads seed[i] after the first wrote crc[i]: the arrays must be disjoint
+    const uintptr_t a = reinterpret_cast<uintptr_t>(d_seed), b = reinterpret_cast<uintptr_t>(d_crc);
+    const uintptr_t bytes = (uintptr_t)n * sizeof(uint32_t);
+    if (a < b + bytes && b < a + bytes) return LNX_EINVAL;
+  }
+  // lnx_crc32_batch's launches into d_crc, then d_crc[i] ^= Z_{len_i}(d_seed[i]) behind them on the stream
+  int st = crc_common(d_bytes, d_off, n, d_crc, false, 0, stream);
+  if (st != LNX_OK || !d_seed) return st;
+  DeviceCtx* c = nullptr;
+  if ((st = get_ctx(&c)) != LNX_OK) return st;
+  const hipError_t e = lnxc::launch_seed_pairs(d_seed, d_off, n, d_crc, c->num_cus, static_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return hip_fail(e, "combine_pairs_kernel (seed) launch");
+  return LNX_OK;
+}
+
+// lnx_crc32_chain_batch / lnx_fcs_verify_chain_batch: lnx_crc32_segments' launch into the caller's d_seg_crc,
+// then the fold of each frame's (CRC, length) pairs.
+static int chain_common(const uint8_t* d_bytes, const uint64_t* d_start, const uint32_t* d_len, uint64_t nseg,
+                        const uint64_t* d_first, uint64_t nframes, const uint32_t* d_seed, uint32_t* d_seg_crc,
+                        void* d_out, bool verify, void* stream) {
+  if (nframes == 0) return LNX_OK;
+  if (!d_first || !d_out) return LNX_EINVAL;
+  if (nseg > 0 && (!d_bytes || !d_start || !d_len || !d_seg_crc)) return LNX_EINVAL;
+  DeviceCtx* c = nullptr;
+  int st = get_ctx(&c);
+  if (st != LNX_OK) return st;
+  const hipStream_t hs = static_cast<hipStream_t>(stream);
+  hipError_t e = launch_crc32_segments(d_bytes, d_start, d_len, nseg, d_seg_crc, c->d_image, c->num_cus, hs);
+  if (e != hipSuccess) return hip_fail(e, "crc32_rows_kernel (segments) launch");
+  e = lnxc::launch_chain_fold(d_seg_crc, d_len, nseg, d_first, nframes, d_seed, d_out, verify, c->num_cus, hs);
+  if (e != hipSuccess) return hip_fail(e, "chain_fold_kernel launch");
+  return LNX_OK;
+}
+
+int lnx_crc32_chain_batch(const uint8_t* d_bytes, const uint64_t* d_start, const uint32_t* d_len, uint64_t nseg,
+                          const uint64_t* d_first, uint64_t nframes, const uint32_t* d_seed, uint32_t* d_seg_crc,
+                          uint32_t* d_crc, void* stream) {
+  return chain_common(d_bytes, d_start, d_len, nseg, d_first, nframes, d_seed, d_seg_crc, d_crc, false, stream);
+}
+
+int lnx_fcs_verify_chain_batch(const uint8_t* d_bytes, const uint64_t* d_start, const uint32_t* d_len, uint64_t nseg,
+                               const uint64_t* d_first, uint64_t nframes, uint32_t* d_seg_crc, uint8_t* d_ok,
+                               void* stream) {
+  return chain_common(d_bytes, d_start, d_len, nseg, d_first, nframes, nullptr, d_seg_crc, d_ok, true, stream);
+}
+
 int lnx_fcs_append_batch(uint8_t* d_bytes, const uint64_t* d_start, uint32_t* d_len, uint64_t n, uint32_t capacity,
                          uint8_t* d_status, void* stream) {
   if (n == 0) return LNX_OK;
@@ -883,7 +958,9 @@ const char* lnx_version(void) {
          "giant slices by span, mean or 8x skew, out-of-order giant slices frame by frame) + rx_verify (FCS and "
          "verdicts in one read: 16-lane rows, 56-frame groups, the next pass loaded ahead, units no frame reaches "
          "skipped) + tx_finish (checksums, padding and FCS in one read, CRC corrected by linearity; 16 waves, "
-         "48-frame groups) + zero copy through the ring's pinned slots";
+         "48-frame groups) + zero copy through the ring's pinned slots + running CRCs (seeds, "
+         "combine, frames made of segments: Z_k by nibble tables of x^(8 * 2^j) in LDS, a 16-lane row or the "
+         "workgroup per frame)";
 }
 
 }  // extern "C"

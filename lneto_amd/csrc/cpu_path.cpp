@@ -62,6 +62,12 @@ uint32_t lnx_crc32_update(uint32_t crc, const uint8_t* p, size_t n) {
 
 uint32_t lnx_crc32(const uint8_t* p, size_t n) { return lnx_crc32_update(0, p, n); }
 
+// CRC32(A || B) = Z_|B|(CRC32(A)) ^ CRC32(B): the init / xorout inversions of
+// the two CRCs cancel, and Z_k is x^(8k) mod P for every 64-bit k (gf2.hpp).
+uint32_t lnx_crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b) {
+  return lnx::zshift_bytes_fast(crc_a, len_b) ^ crc_b;
+}
+
 int64_t lnx_crc32_search(const uint8_t* p, size_t n, int64_t min_off) {
   // ethernet/crc.go:28-47: clamp, length guard, incremental per-byte extension.
   if (min_off < 0) min_off = 0;

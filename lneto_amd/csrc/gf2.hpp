@@ -51,7 +51,7 @@ constexpr uint32_t multmodp(uint32_t a, uint32_t b) {
 }
 
 // x^(8k) mod P for any k >= 0 (square-and-multiply); x^0 is 0x80000000.
-inline uint32_t x8kmodp(uint64_t k) {
+constexpr uint32_t x8kmodp(uint64_t k) {
   uint32_t result = 0x80000000u;
   uint32_t sq = zshift_bytes(0x80000000u, 1);  // x^8
   while (k) {
@@ -63,6 +63,6 @@ inline uint32_t x8kmodp(uint64_t k) {
 }
 
 // Z_k(r) for any k >= 0 in O(log k).
-inline uint32_t zshift_bytes_fast(uint32_t r, uint64_t k) { return multmodp(x8kmodp(k), r); }
+constexpr uint32_t zshift_bytes_fast(uint32_t r, uint64_t k) { return multmodp(x8kmodp(k), r); }
 
 }  // namespace lnx

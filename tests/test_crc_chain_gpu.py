@@ -1,0 +1,335 @@
+"""Running CRCs on the MI355X: lnx_crc32_combine_batch, lnx_crc32_update_batch,
+lnx_crc32_chain_batch and lnx_fcs_verify_chain_batch against zlib over the
+bytes (and the host lnx_crc32_combine for lengths no buffer holds)."""
+import zlib
+
+import numpy as np
+import pytest
+
+import lneto_amd as L
+from lneto_amd import synth
+
+pytestmark = pytest.mark.gpu
+
+SMALL = [0, 1, 2, 3, 4, 5, 59, 60, 64, 1500, 9000, 70000]
+HUGE = [2**31, 2**32 - 1, 2**32, 2**32 + 1, 2**40 + 3, 2**63 + 12345, 2**64 - 1]
+
+
+def dev_u32(a, cuda):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint32).view(np.int32)).to(cuda)
+
+
+def dev_u64(a, cuda):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint64).view(np.int64)).to(cuda)
+
+
+def dev_u8(a, cuda):
+    import torch
+    return torch.from_numpy(np.array(a, dtype=np.uint8)).to(cuda)
+
+
+def host_u32(t):
+    return t.cpu().numpy().view(np.uint32)
+
+
+# ------------------------------------------------------------------ combine
+def test_combine_batch_matches_the_host_function(cuda):
+    rng = np.random.default_rng(11)
+    n = 4099  # not a multiple of 64, more than one workgroup
+    a = rng.integers(0, 2**32, n, dtype=np.uint64).astype(np.uint32)
+    b = rng.integers(0, 2**32, n, dtype=np.uint64).astype(np.uint32)
+    pool = np.array(SMALL + HUGE, dtype=np.uint64)
+    k = np.where(rng.random(n) < 0.5, pool[rng.integers(0, len(pool), n)], rng.integers(0, 2048, n).astype(np.uint64))
+    a[:8], k[8:16] = 0, 0  # zero operands and zero lengths among the rest
+    want = np.array([L.crc32_combine(int(x), int(y), int(z)) for x, y, z in zip(a, b, k)], dtype=np.uint32)
+    da, db, dk = dev_u32(a, cuda), dev_u32(b, cuda), dev_u64(k, cuda)
+    assert np.array_equal(host_u32(L.crc32_combine_batch(da, db, dk)), want)
+    ia = da.clone()
+    assert L.crc32_combine_batch(ia, db, dk, out=ia) is ia  # d_out aliasing d_crc_a
+    assert np.array_equal(host_u32(ia), want)
+    ib = db.clone()
+    L.crc32_combine_batch(da, ib, dk, out=ib)               # d_out aliasing d_crc_b
+    assert np.array_equal(host_u32(ib), want)
+    assert np.array_equal(host_u32(da), a) and np.array_equal(host_u32(db), b)
+
+
+# ------------------------------------------------------------------- update
+def frames_crc(data, off, seeds):
+    """zlib over every frame data[off[i]:off[i+1]] (empty when the end is below the start)."""
+    raw = data.tobytes()
+    out = np.empty(len(off) - 1, dtype=np.uint32)
+    for i in range(len(off) - 1):
+        s, e = int(off[i]), int(off[i + 1])
+        out[i] = zlib.crc32(raw[s:e] if e > s else b"", int(seeds[i]))
+    return out
+
+
+def mixed_seeds(n, rng):
+    s = rng.integers(0, 2**32, n, dtype=np.uint64).astype(np.uint32)
+    s[0::3] = 0
+    s[1::3] = 0xFFFFFFFF
+    return s
+
+
+def test_update_batch_every_length_alignment_and_seed(cuda):
+    rng = np.random.default_rng(12)
+    lens = np.arange(3000) % 301  # every length 0..300
+    off0 = synth.offsets_from_lengths(lens)
+    data = rng.integers(0, 256, int(off0[-1]) + 4, dtype=np.uint8)
+    seeds = mixed_seeds(len(lens), rng)
+    d, ds = dev_u8(data, cuda), dev_u32(seeds, cuda)
+    for base in range(4):
+        off = off0 + np.uint64(base)
+        do = dev_u64(off, cuda)
+        got = host_u32(L.crc32_update_batch(d, do, ds))
+        assert np.array_equal(got, frames_crc(data, off, seeds)), base
+        plain = L.crc32_update_batch(d, do, None)  # no seeds: lnx_crc32_batch
+        assert np.array_equal(host_u32(plain), host_u32(L.crc32_batch(d, do)))
+        assert np.array_equal(host_u32(plain), frames_crc(data, off, np.zeros(len(lens))))
+    assert np.array_equal(host_u32(ds), seeds)
+
+
+def test_update_batch_end_offset_below_start_gives_the_seed(cuda):
+    """An end offset below its start is an empty frame and its result the seed.
+
+    Dense pattern (every 7th of 600 offsets lowered below its predecessor, 85
+    empty frames): every empty frame gives its seed, and every frame gives
+    lnx_crc32_batch's CRC of the same offsets joined with its seed
+    (lnx_crc32_combine on the host), which is how the entry is defined.
+    Against zlib over the bytes the check runs on the out-of-order patterns
+    tests/test_stage.py pins lnx_crc32_batch on (off = [0, 8, 4, 12]; a Zipf
+    batch with single reversed pairs).  On the dense pattern lnx_crc32_batch
+    itself differs from zlib on MI355X for 2 of the 600 frames (259 and 322,
+    each a frame starting at a lowered offset and overlapping its
+    predecessors), with or without seeds; this entry inherits those CRCs."""
+    rng = np.random.default_rng(13)
+    lens = rng.integers(0, 301, 600)
+    off = synth.offsets_from_lengths(lens)
+    off[7::7] -= np.minimum(off[7::7], rng.integers(1, 700, len(off[7::7])).astype(np.uint64))  # out of order
+    data = rng.integers(0, 256, int(off.max()) + 4, dtype=np.uint8)
+    seeds = mixed_seeds(len(lens), rng)
+    empty = off[1:] < off[:-1]
+    assert empty.sum() > 40
+    d, do = dev_u8(data, cuda), dev_u64(off, cuda)
+    got = host_u32(L.crc32_update_batch(d, do, dev_u32(seeds, cuda)))
+    assert np.array_equal(got[empty], seeds[empty])
+    plain = host_u32(L.crc32_batch(d, do))
+    flen = np.where(empty, 0, off[1:] - off[:-1])
+    assert np.array_equal(got, np.array([L.crc32_combine(int(s), int(c), int(n)) for s, c, n in zip(seeds, plain, flen)],
+                                        dtype=np.uint32))
+    zoff = synth.offsets_from_lengths(synth.zipf_lengths(20_000, seed=71)).astype(np.int64)
+    for i in (5, 777, 4_001, 19_990):
+        zoff[i] = zoff[i + 1] + 3  # frame i - 1 runs long, frame i is empty
+    for off in (np.array([0, 8, 4, 12], dtype=np.uint64), zoff.astype(np.uint64)):
+        data = rng.integers(0, 256, int(off.max()) + 4, dtype=np.uint8)
+        seeds = mixed_seeds(len(off) - 1, rng)
+        got = host_u32(L.crc32_update_batch(dev_u8(data, cuda), dev_u64(off, cuda), dev_u32(seeds, cuda)))
+        want = frames_crc(data, off, seeds)
+        assert np.array_equal(got, want), np.nonzero(got != want)[0][:10]
+        empty = off[1:] < off[:-1]
+        assert empty.any() and np.array_equal(got[empty], seeds[empty])
+
+
+def test_update_batch_running_crc_over_two_calls(cuda):
+    rng = np.random.default_rng(14)
+    n = 2000
+    lens = rng.integers(0, 1501, n)
+    cut = (rng.random(n) * (lens + 1)).astype(np.int64)  # 0..len: either part may be empty
+    off = synth.offsets_from_lengths(lens).astype(np.int64)
+    data = rng.integers(0, 256, int(off[-1]), dtype=np.uint8)
+    raw = data.tobytes()
+    head = b"".join(raw[off[i]:off[i] + cut[i]] for i in range(n))
+    tail = b"".join(raw[off[i] + cut[i]:off[i + 1]] for i in range(n))
+    seeds = mixed_seeds(n, rng)
+    ping = L.crc32_update_batch(dev_u8(np.frombuffer(head, np.uint8), cuda),
+                                dev_u64(synth.offsets_from_lengths(cut), cuda), dev_u32(seeds, cuda))
+    d_tail, o_tail = dev_u8(np.frombuffer(tail, np.uint8), cuda), dev_u64(synth.offsets_from_lengths(lens - cut), cuda)
+    pong = L.crc32_update_batch(d_tail, o_tail, ping)
+    assert np.array_equal(host_u32(pong), frames_crc(data, off, seeds))
+    with pytest.raises(L.LnetoError):  # d_seed and d_crc must not overlap
+        L.crc32_update_batch(d_tail, o_tail, ping, out=ping)
+
+
+def test_update_batch_mixed_lengths_take_the_staged_path(cuda):
+    rng = np.random.default_rng(15)
+    lens = synth.zipf_lengths(20000)
+    off = synth.offsets_from_lengths(lens)
+    data = synth.bytes_np(int(off[-1]))
+    seeds = mixed_seeds(len(lens), rng)
+    got = host_u32(L.crc32_update_batch(dev_u8(data, cuda), dev_u64(off, cuda), dev_u32(seeds, cuda)))
+    assert np.array_equal(got, frames_crc(data, off, seeds))
+
+
+# -------------------------------------------------------------------- chains
+def lay_out(frames, rng, pad=0):
+    """Frames (lists of bytes segments) -> (buffer, start, len, first): the segments
+    stored in shuffled address order with gaps; `pad` spare segment entries of
+    non-zero garbage (in-range starts) behind the nseg real ones."""
+    segs = [g for f in frames for g in f]
+    first = np.zeros(len(frames) + 1, dtype=np.uint64)
+    np.cumsum([len(f) for f in frames], out=first[1:])
+    nseg = len(segs)
+    start = np.zeros(nseg + pad, dtype=np.uint64)
+    length = np.zeros(nseg + pad, dtype=np.uint32)
+    pos, order = 0, rng.permutation(nseg)
+    gaps = rng.integers(0, 8, nseg)
+    for j, k in enumerate(order):
+        pos += int(gaps[j])
+        start[k], length[k] = pos, len(segs[k])
+        pos += len(segs[k])
+    buf = rng.integers(0, 256, pos + 64, dtype=np.uint8)
+    for k, g in enumerate(segs):
+        buf[int(start[k]):int(start[k]) + len(g)] = np.frombuffer(g, np.uint8)
+    if pad:
+        start[nseg:] = rng.integers(0, max(pos - 64, 1), pad)
+        length[nseg:] = rng.integers(1, 64, pad)
+    return buf, start, length, first
+
+
+def chain_want(frames, seeds):
+    return np.array([zlib.crc32(b"".join(f), int(s)) for f, s in zip(frames, seeds)], dtype=np.uint32)
+
+
+def random_frames(rng, n, max_segs=9, lens=(0, 1, 3, 4, 7, 60, 1500, 2048)):
+    return [[rng.bytes(int(rng.choice(lens))) for _ in range(int(rng.integers(0, max_segs + 1)))] for _ in range(n)]
+
+
+@pytest.fixture(scope="module")
+def chain_batch(cuda):
+    """3000 frames of 0..9 segments, laid out once for the tests that share it."""
+    rng = np.random.default_rng(16)
+    frames = random_frames(rng, 3000)
+    buf, start, length, first = lay_out(frames, rng)
+    seeds = mixed_seeds(len(frames), rng)
+    dev = (dev_u8(buf, cuda), dev_u64(start, cuda), dev_u32(length, cuda), dev_u64(first, cuda))
+    return frames, seeds, dev
+
+
+def test_chain_batch_matches_zlib_over_the_concatenation(cuda, chain_batch):
+    import torch
+    frames, seeds, (d, ds, dl, df) = chain_batch
+    nseg = ds.numel()
+    ws = torch.full((nseg,), -1, dtype=torch.int32, device=cuda)
+    got = host_u32(L.crc32_chain_batch(d, ds, dl, df, seg_crc=ws))
+    assert np.array_equal(got, chain_want(frames, np.zeros(len(frames))))
+    seg = np.array([zlib.crc32(g) for f in frames for g in f], dtype=np.uint32)
+    assert np.array_equal(host_u32(ws), seg)  # the workspace: every segment's own CRC
+    assert np.array_equal(host_u32(ws), host_u32(L.crc32_segments(d, ds, dl)))
+    got = host_u32(L.crc32_chain_batch(d, ds, dl, df, d_seed=dev_u32(seeds, cuda)))  # workspace from the binding
+    assert np.array_equal(got, chain_want(frames, seeds))
+
+
+def test_chain_batch_long_frames_cross_lanes_and_waves(cuda):
+    rng = np.random.default_rng(17)
+    frames = random_frames(rng, 37)
+    long_lens = rng.integers(1, 65, 5000)
+    long_lens[2000:2300:3] = 0  # empty segments in the middle
+    frames.insert(5, [rng.bytes(int(x)) for x in long_lens])                 # the whole workgroup's fold
+    frames.insert(21, [rng.bytes(int(x)) for x in rng.integers(0, 65, 70)])  # more segments than a row's lanes
+    frames.append([rng.bytes(int(x)) for x in rng.integers(1, 9, 256)])      # the largest frame a row takes
+    frames.append([rng.bytes(int(x)) for x in rng.integers(1, 9, 257)])      # the smallest the workgroup takes
+    buf, start, length, first = lay_out(frames, rng)
+    seeds = mixed_seeds(len(frames), rng)
+    args = (dev_u8(buf, cuda), dev_u64(start, cuda), dev_u32(length, cuda), dev_u64(first, cuda))
+    assert np.array_equal(host_u32(L.crc32_chain_batch(*args, d_seed=dev_u32(seeds, cuda))), chain_want(frames, seeds))
+    assert np.array_equal(host_u32(L.crc32_chain_batch(*args)), chain_want(frames, np.zeros(len(frames))))
+
+
+def test_chain_batch_decreasing_first_pair_is_an_empty_frame(cuda, chain_batch):
+    frames, seeds, (d, ds, dl, df) = chain_batch
+    segs = [g for f in frames for g in f]
+    first = df.cpu().numpy().view(np.uint64).copy()
+    i = 1500
+    first[i] = first[i - 1] - 1 if first[i - 1] else 0  # frame i-1 has no segments; frame i starts below it
+    assert first[i] < first[i - 1] or first[i - 1] == 0
+    want = np.array([zlib.crc32(b"".join(segs[int(first[f]):int(first[f + 1])]), int(seeds[f]))
+                     for f in range(len(frames))], dtype=np.uint32)
+    assert want[i - 1] == seeds[i - 1]
+    got = host_u32(L.crc32_chain_batch(d, ds, dl, dev_u64(first, cuda), d_seed=dev_u32(seeds, cuda)))
+    assert np.array_equal(got, want)
+
+
+def test_chain_batch_clamps_first_to_nseg(cuda):
+    rng = np.random.default_rng(18)
+    frames = random_frames(rng, 200)
+    frames[-1] = [rng.bytes(60), rng.bytes(7)]
+    buf, start, length, first = lay_out(frames, rng, pad=64)
+    nseg = int(first[-1])
+    first[-1] = nseg + 10  # past the segments in use: the garbage entries behind them must not be folded
+    seeds = mixed_seeds(len(frames), rng)
+    ws = dev_u32(rng.integers(1, 2**32, nseg + 64, dtype=np.uint64), cuda)
+    args = (dev_u8(buf, cuda), dev_u64(start, cuda), dev_u32(length, cuda), dev_u64(first, cuda))
+    got = host_u32(L.crc32_chain_batch(*args, d_seed=dev_u32(seeds, cuda), seg_crc=ws, nseg=nseg))
+    assert np.array_equal(got, chain_want(frames, seeds))
+    ok = L.fcs_verify_chain_batch(*args, seg_crc=ws, nseg=nseg).cpu().numpy()
+    assert np.array_equal(ok, (chain_want(frames, np.zeros(len(frames))) == L.CRC32_RESIDUE).astype(np.uint8))
+
+
+def test_chain_batch_without_segments(cuda):
+    import torch
+    empty8 = torch.empty(0, dtype=torch.uint8, device=cuda)
+    empty64 = torch.empty(0, dtype=torch.int64, device=cuda)
+    empty32 = torch.empty(0, dtype=torch.int32, device=cuda)
+    first = dev_u64(np.zeros(6), cuda)
+    seeds = np.array([0, 1, 0xFFFFFFFF, 7, 0x80000000], dtype=np.uint32)
+    got = host_u32(L.crc32_chain_batch(empty8, empty64, empty32, first, d_seed=dev_u32(seeds, cuda)))
+    assert np.array_equal(got, seeds)  # nseg == 0: every frame is empty, its CRC its seed
+    assert not L.fcs_verify_chain_batch(empty8, empty64, empty32, first).cpu().numpy().any()
+
+
+# ---------------------------------------------------------------- FCS verify
+def with_fcs(payload):
+    return payload + zlib.crc32(payload).to_bytes(4, "little")
+
+
+def cut(frame, points):
+    pts = [0] + list(points) + [len(frame)]
+    return [frame[a:b] for a, b in zip(pts[:-1], pts[1:])]
+
+
+def test_fcs_verify_chain_wherever_the_fcs_falls(cuda):
+    rng = np.random.default_rng(19)
+    frames, want = [], []
+    for n in (60, 61, 333, 1514, 9000):
+        f = with_fcs(rng.bytes(n))
+        for tail in (0, 1, 2, 3, 4):  # FCS bytes in the last segment: 4|0, 3|1, 2|2, 1|3, alone
+            frames.append(cut(f, [n // 3, len(f) - tail]))
+            want.append(1)
+    base = len(frames)
+    f = with_fcs(rng.bytes(200))
+    for pos in range(3):  # one flipped byte in each segment position in turn
+        segs = [bytearray(g) for g in cut(f, [100, 202])]
+        segs[pos][len(segs[pos]) // 2] ^= 0x40
+        frames.append([bytes(g) for g in segs])
+        want.append(0)
+    frames.append(cut(f, [100, 202]))
+    want.append(1)
+    for total in range(4):  # too short to hold an FCS
+        frames.append(cut(bytes(total), [total // 2]))
+        want.append(0)
+    frames.append([])
+    want.append(0)
+    args = lay_out(frames, rng)
+    ok = L.fcs_verify_chain_batch(*(fn(a, cuda) for fn, a in zip((dev_u8, dev_u64, dev_u32, dev_u64), args)))
+    ok = ok.cpu().numpy()
+    assert ok.dtype == np.uint8 and np.array_equal(ok, np.array(want, dtype=np.uint8)), (ok, base)
+
+
+def test_fcs_verify_chain_of_one_segment_equals_fcs_verify_batch(cuda):
+    rng = np.random.default_rng(20)
+    lens = np.concatenate([np.arange(0, 70), rng.integers(60, 1515, 930)])
+    off = synth.offsets_from_lengths(lens + 4)
+    raw = bytearray()
+    for i, n in enumerate(lens):
+        f = bytearray(with_fcs(rng.bytes(int(n))))
+        if i % 3 == 0:
+            f[int(rng.integers(0, len(f)))] ^= 1
+        raw += f
+    d, do = dev_u8(np.frombuffer(bytes(raw), np.uint8), cuda), dev_u64(off, cuda)
+    chain = L.fcs_verify_chain_batch(d, dev_u64(off[:-1], cuda), dev_u32(lens + 4, cuda),
+                                     dev_u64(np.arange(len(lens) + 1), cuda))
+    flat = L.fcs_verify_batch(d, do)
+    assert np.array_equal(chain.cpu().numpy(), flat.cpu().numpy())
+    assert 0 < int(flat.sum()) < len(lens)
