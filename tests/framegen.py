@@ -400,3 +400,154 @@ def pcap_frames(seed: int = 31, count: int = 2400) -> list[bytes]:
             f = bytes(b)
         out.append(f)
     return base + out
+
+
+# ------------------------------------------------ frames at the 16-bit limits
+LIMIT_KINDS4 = ("tcp4", "udp4", "icmp4", "tcp4opt")   # IPv4; tcp4opt: 40 option bytes (IHL 15)
+LIMIT_KINDS6 = ("tcp6", "udp6", "icmp6")
+LIMIT_TL4 = (65535, 65534, 65533, 32769)              # IPv4 total length
+LIMIT_PL6 = (65535, 65534, 32769)                     # IPv6 payload length
+LIMIT_FILLS = ("ff", "00", "ff00", "00ff", "rand")
+LIMIT_VARIANTS4 = ("flip_last", "flip_first", "trail1", "trail4097", "cut1", "udp_len_plus1", "bad_hdr")
+LIMIT_VARIANTS6 = ("flip_last", "flip_first", "trail1", "trail4097", "cut1")
+
+
+def limit_fill(fill: str, n: int, rng) -> bytes:
+    """n payload bytes: all 0xFF / all 0x00 (the even- and odd-offset byte sums
+    E and O both at their maximum / minimum), FF 00 / 00 FF repeated (one of
+    them at its maximum, the other 0), or random."""
+    if fill == "rand":
+        return rng.integers(0, 256, n, dtype=np.uint8).tobytes()
+    unit = {"ff": b"\xff\xff", "00": b"\0\0", "ff00": b"\xff\x00", "00ff": b"\x00\xff"}[fill]
+    return (unit * ((n + 1) // 2))[:n]
+
+
+def _limit_packet(kind: str, n_l4: int, fill: str, rng, fix_l4: bool = True) -> bytes:
+    """One Ethernet frame of `kind` whose transport data (header included) has n_l4 bytes."""
+    hdr = 20 if kind.startswith("tcp") else 8
+    pay = limit_fill(fill, n_l4 - hdr, rng)
+    if kind in ("tcp4", "tcp4opt"):
+        return ether(0x0800, ipv4(6, tcp(pay), opts=bytes(40) if kind == "tcp4opt" else b"", fix_l4=fix_l4))
+    if kind == "udp4":
+        return ether(0x0800, ipv4(17, udp(pay), fix_l4=fix_l4))
+    if kind == "icmp4":
+        return ether(0x0800, ipv4(1, icmp(8, pay), fix_l4=fix_l4))
+    if kind == "tcp6":
+        return ether(0x86DD, ipv6(6, tcp(pay), fix_l4=fix_l4))
+    if kind == "udp6":
+        return ether(0x86DD, ipv6(17, udp(pay), fix_l4=fix_l4))
+    return ether(0x86DD, ipv6(58, icmp(128, pay), fix_l4=fix_l4))
+
+
+def _limit_l4_start(kind: str) -> int:
+    return 54 if kind.endswith("6") else 74 if kind == "tcp4opt" else 34
+
+
+def _limit_variant(frame: bytes, kind: str, variant: str) -> bytes:
+    """A receive variant of a valid frame (the frame ends where tl / pl + 40 does)."""
+    b = bytearray(frame)
+    la = _limit_l4_start(kind)
+    if variant == "flip_last":        # one bit of the last covered byte
+        b[-1] ^= 0x01
+    elif variant == "flip_first":     # one bit of the first transport byte
+        b[la] ^= 0x01
+    elif variant == "trail1":         # non-zero bytes past tl / pl + 40: ignored
+        b += b"\xa5"
+    elif variant == "trail4097":      # ... the frame is then longer than 64 KiB + 14
+        b += bytes(1 + (i * 7) % 255 for i in range(4097))
+    elif variant == "cut1":           # tl / pl + 40 one past the frame
+        del b[-1]
+    elif variant == "udp_len_plus1":  # IPv4 UDP: the UDP length one above the IP payload
+        ul = struct.unpack(">H", b[la + 4:la + 6])[0]
+        b[la + 4:la + 6] = struct.pack(">H", ul + 1)
+    elif variant == "bad_hdr":        # IPv4: a valid transport sum behind a broken header sum (TTL)
+        b[22] ^= 0x01
+    else:
+        raise ValueError(variant)
+    return bytes(b)
+
+
+def _limit_garble(frame: bytes, kind: str, rng) -> bytes:
+    """Garbage in every field the transmit checksum step writes."""
+    b = bytearray(frame)
+    la = _limit_l4_start(kind)
+    at = [18] if kind.endswith("6") else [16, 24]
+    at += {"tcp": [la + 16], "udp": [la + 4, la + 6], "icm": [la + 2]}[kind[:3]]
+    for o in at:
+        b[o:o + 2] = rng.integers(0, 256, 2, dtype=np.uint8).tobytes()
+    return bytes(b)
+
+
+def _limit_zero_sum(kind: str, n_l4: int, fill: str, rng) -> bytes:
+    """A frame of `kind` whose transport checksum computes to 0: the last whole
+    16-bit word of the transport data is set to the checksum the data has with
+    that word (and the checksum field) zero; the field itself is left 0."""
+    f = bytearray(_limit_packet(kind, n_l4, fill, rng, fix_l4=False))
+    la = _limit_l4_start(kind)
+    at = la + (16 if kind.startswith("tcp") else 6)
+    w = la + ((n_l4 - 2) & ~1)
+    f[at:at + 2] = b"\0\0"
+    f[w:w + 2] = b"\0\0"
+    g, st = O.tx_checksum(bytes(f))
+    assert st == 0
+    c = g[at:at + 2]
+    f[w:w + 2] = b"\0\0" if c == b"\xff\xff" and kind.startswith("udp") else c  # (NeverZeroSum: the sum was 0 already)
+    return bytes(f)
+
+
+def limit_frames(seed: int = 65535) -> list[tuple[str, bytes]]:
+    """(name, frame) pairs at the largest lengths lneto's stack accepts (any IPv4
+    total length and IPv6 payload length up to 65535: internet/stack-ip4.go:100-107,
+    internet/stack-ip6.go:86-138) with payloads that saturate the checksum
+    accumulators.  Deterministic.
+
+    rx/<kind>/<length>/<fill>/asis: every kind (LIMIT_KINDS4 x LIMIT_TL4,
+      LIMIT_KINDS6 x LIMIT_PL6) x LIMIT_FILLS, valid; each followed by one
+      receive variant of it (LIMIT_VARIANTS4 / LIMIT_VARIANTS6 in rotation, so
+      that every variant meets every fill).
+    twin/...: a maximum-size TCP frame whose correct checksum is 0x0000 with the
+      field 0x0000 and with 0xFFFF (both valid), and maximum-size IPv4 / IPv6
+      UDP frames whose sum computes to 0, carrying 0xFFFF (NeverZeroSum).
+    tx/<kind>/<L - 14 or L - 54>/<fill>: transmit inputs with garbage in every
+      field the step writes, at the largest length the step accepts (every
+      fill) and one byte more (status 15, frame untouched; one fill each, in
+      rotation); and the zero-sum UDP frames with a garbled checksum field."""
+    rng = np.random.default_rng(seed)
+    out = []
+    for kinds, lengths, variants, extra in ((LIMIT_KINDS4, LIMIT_TL4, LIMIT_VARIANTS4, 20),
+                                            (LIMIT_KINDS6, LIMIT_PL6, LIMIT_VARIANTS6, 0)):
+        i = 0
+        for kind in kinds:
+            for length in lengths:
+                n_l4 = length - extra - (40 if kind == "tcp4opt" else 0)
+                for fill in LIMIT_FILLS:
+                    f = _limit_packet(kind, n_l4, fill, rng)
+                    out.append((f"rx/{kind}/{length}/{fill}/asis", f))
+                    v = variants[(i + i // len(LIMIT_FILLS)) % len(variants)]
+                    if v == "udp_len_plus1" and kind != "udp4":
+                        v = "bad_hdr"
+                    out.append((f"rx/{kind}/{length}/{fill}/{v}", _limit_variant(f, kind, v)))
+                    i += 1
+    z = _limit_zero_sum("tcp4", 65535 - 20, "ff", rng)
+    out.append(("twin/tcp4/65535/sum_0000", z))
+    out.append(("twin/tcp4/65535/sum_ffff", z[:50] + b"\xff\xff" + z[52:]))
+    zero_udp = []
+    for kind, n_l4, at in (("udp4", 65535 - 20, 40), ("udp6", 65535, 60)):
+        z = _limit_zero_sum(kind, n_l4, "rand", rng)
+        z = z[:at] + b"\xff\xff" + z[at + 2:]
+        zero_udp.append((kind, z))
+        out.append((f"twin/{kind}/65535/sum_zero", z))
+    j = 0
+    for kinds, top, extra in ((LIMIT_KINDS4, 65535, 20), (LIMIT_KINDS6, 65535, 0)):
+        for kind in kinds:
+            n_l4 = top - extra - (40 if kind == "tcp4opt" else 0)
+            for fill in LIMIT_FILLS:
+                f = _limit_garble(_limit_packet(kind, n_l4, fill, rng, fix_l4=False), kind, rng)
+                out.append((f"tx/{kind}/{top}/{fill}", f))
+            fill = LIMIT_FILLS[j % len(LIMIT_FILLS)]
+            f = _limit_garble(_limit_packet(kind, n_l4, fill, rng, fix_l4=False), kind, rng)
+            out.append((f"tx/{kind}/{top + 1}/{fill}", f + limit_fill(fill, 2, rng)[-1:]))
+            j += 1
+    for kind, z in zero_udp:
+        out.append((f"tx/{kind}/65535/sum_zero", _limit_garble(z, kind, rng)))
+    return out
