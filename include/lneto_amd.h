@@ -22,7 +22,14 @@
  *  - batch entry points return LNX_OK (0) or a negative LNX_E* code and never
  *    abort; per-frame checksum functions return values, never errors;
  *  - `stream` is a hipStream_t passed as an opaque pointer (NULL = the null
- *    stream of the current device); batch calls are asynchronous on it.
+ *    stream of the current device); batch calls are asynchronous on it;
+ *  - batch entry points may be called from any number of host threads at once,
+ *    on the same stream or on different ones.  Calls that several threads make
+ *    on one stream take effect in some order, each call whole (its launches
+ *    are never interleaved with another call's on that stream); calls on
+ *    different streams never wait for each other's device work.  The caller
+ *    still orders what it must: a call that reads what another wrote goes
+ *    after it on the stream.
  */
 #ifndef LNETO_AMD_H
 #define LNETO_AMD_H

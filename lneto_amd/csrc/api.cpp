@@ -5,6 +5,7 @@
 #include <atomic>
 #include <cstdint>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -263,20 +264,32 @@ struct DeviceCtx {
   uint32_t* d_stage = nullptr;   // crc32_stage_kernel image
   uint32_t* d_rx = nullptr;      // rx_verify_kernel image
   // Per stream: the staged kernel's giant-slice slots (stage_kernel.hip
-  // giant_pieces; zero between launches).  Launches on one stream run in
-  // order, so each stream owns one set; streams never share one.
-  // hipStreamPerThread names a different stream in every thread, so it is
-  // keyed by thread too.  At most kGiantStreams sets live per device; the
-  // least recently used one is freed (after a device sync) to make room.
+  // giant_pieces; zero between launches) and the gate words of the two-launch
+  // entries.  Launches on one stream run in order, so each stream owns one
+  // set; streams never share one.  hipStreamPerThread names a different stream
+  // in every thread, so it is keyed by thread too.  At most kGiantStreams sets
+  // live per device; the least recently used one that no call holds is freed
+  // (after a device sync) to make room.
+  //
+  // Who holds what: giant_mu guards the list, the clock and
+  // every set's pins, and is held only while a call looks its set up or makes
+  // one.  A call then takes its set's own mutex, draws its epoch under it and
+  // keeps it until its last launch that uses the epoch is enqueued
+  // (ScratchHold), so the launches of one call reach the stream as a unit with
+  // respect to every other call on that set.  The sets are heap objects: their
+  // addresses outlive the list's reallocations, and a set with pins > 0 is
+  // never evicted.
   struct GiantScratch {
     hipStream_t stream;
     std::thread::id thread;
     uint32_t* p;
-    uint64_t used;   // use counter at the last call
-    uint32_t epoch;  // the last call's epoch (the staged launch's flag word, kStageFlag)
+    uint64_t used = 0;          // use counter at the last call (under giant_mu)
+    std::atomic<int> pins{0};   // calls between lookup and release (raised under giant_mu)
+    std::mutex mu;              // held while a call enqueues its launches
+    uint32_t epoch = 0;         // the last call's epoch (under mu): the gate words' value
   };
   std::mutex giant_mu;
-  std::vector<GiantScratch> giant;
+  std::vector<std::unique_ptr<GiantScratch>> giant;
   uint64_t giant_clock = 0;
 #ifdef LNX_RESEARCH
   // Per-stream scratch of the two-launch TX append (the CRCs between its
@@ -401,42 +414,74 @@ constexpr uint64_t kIngressShortMean = 1280;
 // ... and the generate rows against tx_finish's checksum step (sampled mean)
 constexpr uint64_t kTxChecksumShortMean = 896;
 
-// The calling device's giant-slice scratch for `stream`, zeroed on that
-// stream when made (stream order puts the zeroing before the first launch).
-constexpr size_t kGiantStreams = 32;
-int giant_scratch(DeviceCtx* c, hipStream_t stream, uint32_t** out, uint32_t* epoch) {
-  std::lock_guard<std::mutex> lk(c->giant_mu);
-  const std::thread::id tid = stream == hipStreamPerThread ? std::this_thread::get_id() : std::thread::id();
-  ++c->giant_clock;
-  for (auto& g : c->giant)
-    if (g.stream == stream && g.thread == tid) {
-      g.used = c->giant_clock;
-      g.epoch = g.epoch + 1u == 0u ? 1u : g.epoch + 1u;
-      *out = g.p;
-      *epoch = g.epoch;
-      return LNX_OK;
-    }
-  hipError_t e;
-  if (c->giant.size() >= kGiantStreams) {
-    // its stream may still run a launch on it (or be gone): wait for the device
-    auto lru = std::min_element(c->giant.begin(), c->giant.end(),
-                                [](const DeviceCtx::GiantScratch& a, const DeviceCtx::GiantScratch& b) {
-                                  return a.used < b.used;
-                                });
-    if ((e = hipDeviceSynchronize()) != hipSuccess) return hip_fail(e, "hipDeviceSynchronize(giant-slice scratch)");
-    (void)hipFree(lru->p);
-    c->giant.erase(lru);
-  }
+// A call's hold on its stream's scratch set: the set's mutex, from the epoch
+// until the call's last gated launch is enqueued.  Releasing it unlocks the
+// set and lets it be evicted again.
+struct ScratchHold {
+  DeviceCtx::GiantScratch* g = nullptr;
   uint32_t* p = nullptr;
-  e = hipMalloc(reinterpret_cast<void**>(&p), kScratchWords * sizeof(uint32_t));
-  if (e != hipSuccess) return hip_fail(e, "hipMalloc(giant-slice scratch)");
-  if ((e = hipMemsetAsync(p, 0, kScratchWords * sizeof(uint32_t), stream)) != hipSuccess) {
-    (void)hipFree(p);
-    return hip_fail(e, "hipMemsetAsync(giant-slice scratch)");
+  uint32_t epoch = 0;
+  ScratchHold() = default;
+  ScratchHold(const ScratchHold&) = delete;
+  ScratchHold& operator=(const ScratchHold&) = delete;
+  ~ScratchHold() {
+    if (!g) return;
+    g->mu.unlock();
+    g->pins.fetch_sub(1, std::memory_order_release);
   }
-  c->giant.push_back({stream, tid, p, c->giant_clock, 1u});
-  *out = p;
-  *epoch = 1u;
+};
+
+// The calling device's giant-slice scratch for `stream`, zeroed on that
+// stream when made (stream order puts the zeroing before the first launch),
+// locked for the caller with a new epoch (nonzero, new every call on the set).
+// The wait for the set's mutex is for another thread's enqueue on the same
+// stream only, and happens outside giant_mu: calls on other streams go on.
+constexpr size_t kGiantStreams = 32;
+int giant_scratch(DeviceCtx* c, hipStream_t stream, ScratchHold* hold) {
+  const std::thread::id tid = stream == hipStreamPerThread ? std::this_thread::get_id() : std::thread::id();
+  DeviceCtx::GiantScratch* g = nullptr;
+  while (!g) {
+    std::unique_lock<std::mutex> lk(c->giant_mu);
+    ++c->giant_clock;
+    for (auto& x : c->giant)
+      if (x->stream == stream && x->thread == tid) g = x.get();
+    if (!g) {
+      hipError_t e;
+      if (c->giant.size() >= kGiantStreams) {
+        // the least recently used set that no call holds; its stream may still
+        // run a launch on it (or be gone): wait for the device
+        auto lru = c->giant.end();
+        for (auto it = c->giant.begin(); it != c->giant.end(); ++it)
+          if ((*it)->pins.load(std::memory_order_acquire) == 0 && (lru == c->giant.end() || (*it)->used < (*lru)->used))
+            lru = it;
+        if (lru == c->giant.end()) {  // every set is mid-call (kGiantStreams threads at once): let one finish
+          lk.unlock();
+          std::this_thread::yield();
+          continue;
+        }
+        if ((e = hipDeviceSynchronize()) != hipSuccess) return hip_fail(e, "hipDeviceSynchronize(giant-slice scratch)");
+        (void)hipFree((*lru)->p);
+        c->giant.erase(lru);
+      }
+      uint32_t* p = nullptr;
+      e = hipMalloc(reinterpret_cast<void**>(&p), kScratchWords * sizeof(uint32_t));
+      if (e != hipSuccess) return hip_fail(e, "hipMalloc(giant-slice scratch)");
+      if ((e = hipMemsetAsync(p, 0, kScratchWords * sizeof(uint32_t), stream)) != hipSuccess) {
+        (void)hipFree(p);
+        return hip_fail(e, "hipMemsetAsync(giant-slice scratch)");
+      }
+      c->giant.push_back(std::make_unique<DeviceCtx::GiantScratch>());
+      g = c->giant.back().get();
+      g->stream = stream, g->thread = tid, g->p = p;
+    }
+    g->used = c->giant_clock;
+    g->pins.fetch_add(1, std::memory_order_relaxed);
+  }
+  g->mu.lock();
+  g->epoch = g->epoch + 1u == 0u ? 1u : g->epoch + 1u;
+  hold->g = g;
+  hold->p = g->p;
+  hold->epoch = g->epoch;
   return LNX_OK;
 }
 
@@ -453,9 +498,10 @@ int crc_offsets(const uint8_t* d_bytes, const uint64_t* d_off, uint64_t n, void*
   DeviceCtx* c = nullptr;
   int st = get_ctx(&c);
   if (st != LNX_OK) return st;
-  uint32_t* scratch = nullptr;
-  uint32_t epoch = 0;
-  if ((st = giant_scratch(c, stream, &scratch, &epoch)) != LNX_OK) return st;
+  ScratchHold hold;  // until both launches are enqueued
+  if ((st = giant_scratch(c, stream, &hold)) != LNX_OK) return st;
+  uint32_t* const scratch = hold.p;
+  const uint32_t epoch = hold.epoch;
   hipError_t e = hipSuccess;
   // auto: the rows launch stores the epoch in the flag word when a slice is
   // not its own, and the staged launch behind it exits at once otherwise
@@ -683,9 +729,10 @@ int lnx_tx_checksum_batch(uint8_t* d_bytes, const uint64_t* d_start, const uint3
   // generate rows, or for a batch whose sampled mean frame is under
   // kTxChecksumShortMean bytes tx_finish with the checksum step only
   const hipStream_t hs = static_cast<hipStream_t>(stream);
-  uint32_t* scratch = nullptr;
-  uint32_t epoch = 0;
-  if ((st = giant_scratch(c, hs, &scratch, &epoch)) != LNX_OK) return st;
+  ScratchHold hold;  // until both launches are enqueued
+  if ((st = giant_scratch(c, hs, &hold)) != LNX_OK) return st;
+  uint32_t* const scratch = hold.p;
+  const uint32_t epoch = hold.epoch;
   uint32_t* gate = scratch + kTxChecksumGate;
   hipError_t e = launch_tx_checksum(d_bytes, d_start, d_len, n, d_status, c->num_cus, hs, gate, epoch,
                                     kTxChecksumShortMean);
@@ -742,9 +789,10 @@ int lnx_ingress_verify_batch_filtered(const uint8_t* d_bytes, const uint64_t* d_
   // bytes, else the receive check without its CRC (rx_verify_kernel: the same
   // verdicts, no ok output), gated by a word of the stream's scratch
   const hipStream_t hs = static_cast<hipStream_t>(stream);
-  uint32_t* scratch = nullptr;
-  uint32_t epoch = 0;
-  if ((st = giant_scratch(c, hs, &scratch, &epoch)) != LNX_OK) return st;
+  ScratchHold hold;  // until both launches are enqueued
+  if ((st = giant_scratch(c, hs, &hold)) != LNX_OK) return st;
+  uint32_t* const scratch = hold.p;
+  const uint32_t epoch = hold.epoch;
   uint32_t* gate = scratch + kIngressGate;
   const uint32_t vf = flags & (LNX_VERIFY_EVIL_BIT | LNX_VERIFY_ICMP);
   hipError_t e = launch_ingress_verify(d_bytes, d_off, n, vf, d_verdict, c->num_cus, hs, nullptr, 0, &filt, gate, epoch,

@@ -2,7 +2,10 @@
 scratch and the staged launch's flag word are per stream, zeroed on that
 stream when made, keyed per thread for hipStreamPerThread, and at most 32 live
 per device (the least recently used one freed after a device sync).  GPU
-tests through the C-ABI against the C oracle (ethernet/crc.go:19-21)."""
+tests through the C-ABI against the C oracle (ethernet/crc.go:19-21).  The
+giant CRC shape only: the gate words of the two-launch entries, sequences of
+different kinds on one stream and host threads that share a stream are in
+tests/test_call_sequences.py."""
 import ctypes
 import threading
 
