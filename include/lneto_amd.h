@@ -74,7 +74,8 @@ uint32_t lnx_crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b);
 
 /* Go: ethernet.CRC32Search(data, minOffCRC) (ethernet/crc.go:28-47).
  * First off >= max(minOff,0) with CRC32(data[:off]) == LE32(data[off:]),
- * or -1. */
+ * or -1.  The result is -1 for every int64 min_off above n - 4 (Go panics on
+ * a minOffCRC past the data; no sum of min_off overflows here). */
 int64_t lnx_crc32_search(const uint8_t* p, size_t n, int64_t min_off);
 
 /* Go: sumWriteEven (crc.go:23-28) — uint32 wrap-around sum of big-endian
@@ -313,7 +314,8 @@ int lnx_sum16_batch(const uint8_t* d_bytes, const uint64_t* d_off, const uint32_
  * d_result[i] = CRC32Search(d_bytes[d_off[i] : d_off[i+1]], d_min_off[i]) —
  * the first off >= max(minOff, 0) with CRC32(capture[:off]) ==
  * LE32(capture[off:off+4]), or -1 (also when the capture is shorter than
- * minOff + 4).  d_min_off may be NULL (all 0).  For PIO captures of unknown
+ * minOff + 4: the result is -1 for every int64 d_min_off[i] above len - 4, up
+ * to 2^63 - 1).  d_min_off may be NULL (all 0).  For PIO captures of unknown
  * frame length (phy/rmii.md:265-271); every prefix CRC of a capture is
  * computed in one parallel scan.  d_off may be in any order: an end offset
  * below its start is an empty capture (-1), every other capture, overlapping

@@ -85,6 +85,7 @@ inline uint32_t CRC32(Bytes data) { return lnx_crc32(data.p, data.n); }
 // CRC32(A || B) from CRC32(A), CRC32(B) and len(B); CRC32Combine(seed, CRC32(B), len(B)) == CRC32Update(seed, B).
 inline uint32_t CRC32Combine(uint32_t crcA, uint32_t crcB, uint64_t lenB) { return lnx_crc32_combine(crcA, crcB, lenB); }
 
+// -1 for every minOffCRC above len(data) - 4.
 inline int CRC32Search(Bytes data, int minOffCRC) {
   return (int)lnx_crc32_search(data.p, data.n, minOffCRC);
 }
@@ -126,7 +127,8 @@ inline int VerifyFCSChainBatch(const uint8_t* d_bytes, const uint64_t* d_start, 
                                void* stream = nullptr) {
   return lnx_fcs_verify_chain_batch(d_bytes, d_start, d_len, nseg, d_first, nframes, d_segCRC, d_ok, stream);
 }
-// CRC32Search over every capture bytes[off[i] : off[i+1]] (ethernet/crc.go:28-47).
+// CRC32Search over every capture bytes[off[i] : off[i+1]] (ethernet/crc.go:28-47);
+// -1 for every int64 d_minOffCRC[i] above the capture's length - 4.
 inline int CRC32SearchBatch(const uint8_t* d_bytes, const uint64_t* d_off, const int64_t* d_minOffCRC, uint64_t n,
                             int64_t* d_found, void* stream = nullptr) {
   return lnx_crc32_search_batch(d_bytes, d_off, d_minOffCRC, n, d_found, stream);

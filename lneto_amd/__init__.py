@@ -189,7 +189,7 @@ def crc32_combine(crc_a: int, crc_b: int, len_b: int) -> int:
 
 
 def crc32_search(p: bytes, min_off: int) -> int:
-    """ethernet.CRC32Search (ethernet/crc.go:28-47)."""
+    """ethernet.CRC32Search (ethernet/crc.go:28-47); -1 for every int64 min_off above len(p) - 4."""
     b, n = _buf(p)
     return lib.lnx_crc32_search(b, n, min_off)
 
@@ -528,7 +528,8 @@ def tx_finish_batch(d_bytes, d_start, d_len, capacity: int, flags: int = 3, stat
 
 def crc32_search_batch(d_bytes, d_off, d_min_off=None, out=None, stream=None):
     """ethernet.CRC32Search of every capture d_bytes[d_off[i]:d_off[i+1]] on the GPU
-    (lnx_crc32_search_batch).  d_min_off: int64 (N) or None.  Returns int64 (N), -1 = none."""
+    (lnx_crc32_search_batch).  d_min_off: int64 (N) or None (all 0).  Returns int64 (N), -1 = none:
+    also for every int64 d_min_off[i] above the capture's length - 4."""
     import torch
     what = "lnx_crc32_search_batch"
     b = _Batch(what, [("d_bytes", d_bytes, "u8"), ("d_off", d_off, "i64"), ("d_min_off", d_min_off, "i64?")],

@@ -71,7 +71,8 @@ uint32_t lnx_crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b) {
 int64_t lnx_crc32_search(const uint8_t* p, size_t n, int64_t min_off) {
   // ethernet/crc.go:28-47: clamp, length guard, incremental per-byte extension.
   if (min_off < 0) min_off = 0;
-  if ((int64_t)n < min_off + 4) return -1;
+  // -1 for every min_off above n - 4, decided without min_off + 4 (it wraps near 2^63)
+  if (n < 4 || n - 4 < (uint64_t)min_off) return -1;
   uint32_t crc = lnx_crc32(p, (size_t)min_off);
   for (int64_t off = min_off; off <= (int64_t)n - 4; ++off) {
     if (crc == load_le32(p + off)) return off;

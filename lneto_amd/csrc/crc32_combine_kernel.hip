@@ -303,7 +303,8 @@ chain_fold_kernel(const uint32_t* __restrict__ seg_crc, const uint32_t* __restri
 }
 
 namespace {
-// 16 KiB of LDS and four waves per workgroup: eight fill a CU's 32 wave slots.
+// 16 KiB of LDS and four waves per workgroup: eight fill a CU's 32 wave slots
+// (the cap is restated in tests/test_grid_passes.py LAUNCH).
 unsigned grid_for(uint64_t items, uint64_t per_block, int num_cus) {
   const uint64_t want = (items + per_block - 1) / per_block, cap = (uint64_t)(num_cus > 0 ? num_cus : 1) * 8;
   return (unsigned)(want < cap ? want : cap);

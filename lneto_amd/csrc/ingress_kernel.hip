@@ -594,7 +594,7 @@ hipError_t launch_ingress_verify(const uint8_t* bytes, const uint64_t* off, uint
                        off, n, flags, verdict, seg_len, trim, filt, gate, epoch, short_mean);
   else
 #else
-  const uint64_t cap = (uint64_t)num_cus * 128;
+  const uint64_t cap = (uint64_t)num_cus * 128;  // restated in tests/test_grid_passes.py LAUNCH
   if (grid > cap) grid = cap;
 #endif
   if (filt.on)
@@ -631,7 +631,7 @@ hipError_t launch_tx_checksum(uint8_t* bytes, const uint64_t* start, const uint3
   if (n == 0) return hipSuccess;
   const uint64_t frames_per_block = (kIngBlock / 64) * 4;
   uint64_t grid = (n + frames_per_block - 1) / frames_per_block;
-  const uint64_t cap = (uint64_t)num_cus * 128;
+  const uint64_t cap = (uint64_t)num_cus * 128;  // restated in tests/test_grid_passes.py LAUNCH
   if (grid > cap) grid = cap;
   if (gate) hipLaunchKernelGGL(tx_gate_probe_kernel, dim3(1), dim3(64), 0, stream, len, n, short_mean, gate, epoch);
   hipLaunchKernelGGL((ingress_verify_kernel<kIngUnrollQ, true, true>), dim3((unsigned)grid), dim3(kIngBlock), 0,

@@ -20,7 +20,7 @@ crc32_search_kernel(const uint8_t* __restrict__ bytes, const uint64_t* __restric
     int64_t m = min_off ? min_off[c] : 0;
     if (m < 0) m = 0;
     int64_t found = -1;
-    if (L >= m + 4) {
+    if (L - 4 >= m) {  // not m + 4: it wraps for m near 2^63
       const uint8_t* d = bytes + s;
       uint32_t carry = 0xFFFFFFFFu;  // register entering the block (CRC init)
       // only blocks that can hold a state index k in [m + 4, L] matter, but the

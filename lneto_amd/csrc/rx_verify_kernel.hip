@@ -1371,7 +1371,7 @@ hipError_t launch_rx_verify(const uint8_t* bytes, const uint64_t* off, uint64_t 
   if (filter) filt = *filter;
   if (n == 0) return hipSuccess;
   uint64_t grid = (n + (kRvBlock / 64) * kRvGroup - 1) / ((kRvBlock / 64) * kRvGroup);
-  if (grid > (uint64_t)num_cus) grid = (uint64_t)num_cus;
+  if (grid > (uint64_t)num_cus) grid = (uint64_t)num_cus;  // restated in tests/test_grid_passes.py RV_WAVES, RV_GROUP
   const uint32_t gsz = balanced_group(n, grid * (kRvBlock / 64), kRvGroup);
 #define LNX_RV(C, F, H)                                                                                       \
   hipLaunchKernelGGL((rx_verify_kernel<C, F, H>), dim3((unsigned)grid), dim3(kRvBlock), 0, stream, bytes, off, n, \

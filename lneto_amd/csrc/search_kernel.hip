@@ -94,7 +94,7 @@ crc32_search_seg_kernel(const uint8_t* __restrict__ bytes, const uint64_t* __res
     int64_t m = min_off ? min_off[c] : 0;
     if (m < 0) m = 0;
     int64_t found = -1;
-    if (L >= m + 4) {
+    if (L - 4 >= m) {  // not m + 4: it wraps for m near 2^63
       const uint8_t* d = bytes + s;
       uint32_t carry = 0xFFFFFFFFu;  // register entering the block (CRC init)
       for (int64_t B = 0; B < L && found < 0; B += 64 * SEG) {
@@ -270,7 +270,7 @@ __device__ __forceinline__ void search_half_body(uint32_t* lds, const uint8_t* _
     int64_t m = live && min_off ? min_off[c] : 0;
     if (m < 0) m = 0;
     int64_t found = -1;
-    bool act = live && L >= m + 4;  // this half still searching
+    bool act = live && L - 4 >= m;  // this half still searching (not m + 4: it wraps for m near 2^63)
     const uint8_t* d = bytes + s;
     uint32_t carry = 0xFFFFFFFFu;  // register entering the block (CRC init)
     for (int64_t B = 0; __builtin_amdgcn_ballot_w64(act) != 0; B += 32 * SEG) {
@@ -541,7 +541,7 @@ __device__ __forceinline__ void search_u_body(uint32_t* lds, const uint8_t* __re
       m[j] = gc.m[j];
       if (m[j] < 0) m[j] = 0;
       found[j] = -1;
-      act[j] = live[j] && L[j] >= m[j] + 4;
+      act[j] = live[j] && L[j] - 4 >= m[j];  // not m + 4: it wraps for m near 2^63
       d[j] = bytes + s_;
       carry[j] = 0xFFFFFFFFu;
     }
@@ -747,7 +747,7 @@ crc32_search_o_kernel(const uint8_t* __restrict__ bytes, const uint64_t* __restr
     int64_t m = live && min_off ? min_off[c] : 0;
     if (m < 0) m = 0;
     int64_t found = -1;
-    bool act = live && L >= m + 4;
+    bool act = live && L - 4 >= m;  // not m + 4: it wraps for m near 2^63
     uint32_t carry = 0xFFFFFFFFu;
     // the group's bytes through one descriptor when every capture lies inside [off[ga], off[gb])
     const uint64_t gb = ga + 64 / LPC < n ? ga + 64 / LPC : n;
@@ -861,7 +861,7 @@ hipError_t launch_crc32_search(const uint8_t* bytes, const uint64_t* off, const 
   if (n == 0) return hipSuccess;
   auto launch_octets = [&]() {
     uint64_t g1 = ((n + 7) / 8 + kSegBlock / 64 - 1) / (kSegBlock / 64);
-    if (g1 > (uint64_t)num_cus) g1 = (uint64_t)num_cus;
+    if (g1 > (uint64_t)num_cus) g1 = (uint64_t)num_cus;  // restated in tests/test_grid_passes.py LAUNCH
     hipLaunchKernelGGL(crc32_search_o_kernel, dim3((unsigned)g1), dim3(kSegBlock), 0, stream, bytes, off, min_off, n,
                        tables, result);
   };

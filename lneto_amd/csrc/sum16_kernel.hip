@@ -199,7 +199,7 @@ hipError_t launch_sum16_segments(const uint8_t* bytes, const uint64_t* off, cons
   else
 #else
   (void)var;
-  const uint64_t cap = (uint64_t)num_cus * 256;
+  const uint64_t cap = (uint64_t)num_cus * 256;  // restated in tests/test_grid_passes.py LAUNCH
   if (grid > cap) grid = cap;
 #endif
     hipLaunchKernelGGL(sum16_lines_kernel<true>, dim3((unsigned)grid), dim3(kSumBlock), 0, stream, bytes, off,

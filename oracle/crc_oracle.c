@@ -91,7 +91,7 @@ uint32_t oracle_crc32(const uint8_t* p, size_t n) { return oracle_crc32_update(0
 /* ethernet/crc.go:28-47 */
 int64_t oracle_crc32_search(const uint8_t* p, size_t n, int64_t min_off) {
   if (min_off < 0) min_off = 0;                         /* :29-31 */
-  if ((int64_t)n < min_off + 4) return -1;              /* :32-34 */
+  if (n < 4 || n - 4 < (uint64_t)min_off) return -1;    /* :32-34, without min_off + 4 (it wraps near 2^63) */
   uint32_t crc = oracle_crc32(p, (size_t)min_off);      /* :36 */
   for (int64_t off = min_off; off <= (int64_t)n - 4; off++) {  /* :38 */
     uint32_t got = (uint32_t)p[off] | (uint32_t)p[off + 1] << 8 | (uint32_t)p[off + 2] << 16 |

@@ -56,8 +56,11 @@ def test_random_captures(cuda):
 
 
 def test_long_captures_many_blocks(cuda):
-    """Captures spanning several lane blocks (the register carried from block to
-    block), hits in any block, including on block boundaries."""
+    """Captures of one to ten 1536-byte blocks (the register carried from lane
+    7 into the next block), trailing bytes behind the hit into further blocks,
+    hits in any block; every fourth FCS ends on a multiple of 512 bytes, i.e.
+    on every third one a block edge and otherwise inside lane 2 or 5 of the
+    octet kernel (tests/test_search_octets.py sweeps its own edges)."""
     rng = np.random.default_rng(22)
     caps, mins = [], []
     for i in range(400):
@@ -77,11 +80,12 @@ def test_long_captures_many_blocks(cuda):
 
 
 def test_two_captures_per_wave_pairs(cuda):
-    """Captures share a wave (the r2 kernels fold one or two per 32-lane half,
-    crc32_search_u_kernel<2> four per wave): pair a long capture (several 1536-byte blocks, hit
-    late or never) with a short or empty one, in both orders, hits on the
-    1536-byte block edges, and an odd capture count (the last wave's second
-    half has no capture)."""
+    """Captures share a wave (the product kernel folds eight per wave, eight
+    lanes each; the name dates from the kernels that took two): long captures
+    (several 1536-byte blocks, hit late or never) alternate with short or empty
+    ones, in both orders, so every octet holds four of each and its block loop
+    runs on for the long ones; hits on the 1536-byte block edges; an odd
+    capture count (the last wave holds three captures of its eight)."""
     rng = np.random.default_rng(23)
     caps, mins = [], []
     for i in range(301):
@@ -109,8 +113,8 @@ def test_two_captures_per_wave_pairs(cuda):
 
 
 def test_decreasing_offsets_take_the_guarded_loads(cuda):
-    """a group of four captures that do not all lie inside
-    [off[4q], off[4q + 4]) cannot use the group buffer descriptor and takes the
+    """a group of eight captures that do not all lie inside
+    [off[8q], off[8q + 8]) cannot use the group buffer descriptor and takes the
     per-capture guarded loads (search_kernel.hip, gfast false).  Captures laid
     out in reverse order: off = [a0, b0, a1, b1, ...] with a_{k+1} < b_k, so
     capture 2k = [a_k, b_k) is real and capture 2k + 1 (end below start) is
@@ -152,10 +156,12 @@ def test_decreasing_offsets_take_the_guarded_loads(cuda):
 
 @pytest.mark.parametrize("count", [1, 2, 3, 5, 6, 7, 257])
 def test_four_captures_per_wave_groups(cuda, count):
-    """crc32_search_u_kernel<2> folds captures 4q .. 4q + 3 in one wave (two
-    per 32-lane half, side by side): every group size at the end of the batch,
-    and groups whose four captures end in different 1536-byte blocks (the
-    block loop runs until the last of them is done)."""
+    """Batches of fewer captures than the product kernel's wave of eight (1 to
+    7: one partly live wave; the counts were every group size of the four-a-wave
+    kernel the name dates from) and 257 (33 waves, the last with one capture),
+    the captures of a wave ending in different 1536-byte blocks (the block loop
+    runs until the last of them is done).  Counts around 8 and 128 are in
+    tests/test_search_octets.py::test_group_shapes."""
     rng = np.random.default_rng(100 + count)
     caps, mins = [], []
     for i in range(count):
