@@ -89,6 +89,24 @@ uint16_t lnx_sum16(uint32_t sum);
 /* Go: CRC791{sum}.PayloadSum16(p) (crc.go:52-59). */
 uint16_t lnx_sum16_payload(uint32_t sum, const uint8_t* p, size_t n);
 
+/* The raw running sum of CRC791 (crc.go:13-62) over a piece of a packet: with
+ * E / O = the sums of p's bytes at even / odd offsets from p,
+ *   phase & 1 == 0:  sum + 256 E + O   (the piece starts at an even offset of its packet),
+ *   phase & 1 == 1:  sum + E + 256 O   (at an odd offset: the halves of every word swap),
+ * mod 2^32 as the reference's uint32 wraps (crc.go:23-28); an odd last byte is
+ * an even-offset byte, the `<< 8` of crc.go:56.  With phase 0 and even n this is
+ * lnx_sum_write_even (WriteEven, crc.go:30-33); lnx_sum16 of the result with
+ * phase 0 is lnx_sum16_payload (crc.go:52-59).  A checksum over data that
+ * arrives in pieces passes each call the sum so far and phase = the bytes so
+ * far & 1. */
+uint32_t lnx_sum_partial(uint32_t sum, const uint8_t* p, size_t n, int phase);
+
+/* CRC791{seed}.PayloadSum16 (crc.go:52-59) over the concatenation of m
+ * buffers seg[k][0 : len[k]] (a header buffer plus a payload buffer, a frame
+ * in several ring slots); empty buffers (their pointers are not read) and
+ * m == 0 (sum16 of the seed, crc.go:17-21) are valid. */
+uint16_t lnx_sum16_chain(uint32_t seed, const uint8_t* const* seg, const size_t* len, size_t m);
+
 /* Go: lneto.NeverZeroSum (crc.go:65-71). */
 uint16_t lnx_never_zero_sum(uint16_t sum16);
 
@@ -309,6 +327,50 @@ int lnx_fcs_verify_batch(const uint8_t* d_bytes, const uint64_t* d_off, uint64_t
  * ipv6.Frame.CRCWritePseudo (ipv6/frame.go:104-108). */
 int lnx_sum16_batch(const uint8_t* d_bytes, const uint64_t* d_off, const uint32_t* d_len,
                     const uint32_t* d_seed, uint64_t n, uint16_t* d_out, void* stream);
+
+/* ---- running internet checksums: raw sums, odd phase, frames made of segments ----
+ * As every batch entry these are asynchronous on `stream`, never sync, never
+ * read device memory on the host, never allocate and retain nothing; they use
+ * no scratch.  A zero count returns LNX_OK; a NULL required pointer with a
+ * non-zero count LNX_EINVAL. */
+
+/* The raw 32-bit running sum of n segments (lnx_sum_partial; sumWriteEven /
+ * WriteEven, crc.go:23-33, and the odd last byte of crc.go:56):
+ *   d_sum[i] = lnx_sum_partial(d_seed ? d_seed[i] : 0, d_bytes[d_off[i] : d_off[i] + d_len[i]], d_phase ? d_phase[i] : 0).
+ * d_phase holds one byte per segment of which only bit 0 is read (the parity
+ * of the segment's offset in its packet); NULL = every segment at an even
+ * offset.  Segments may lie in any order and overlap, as for lnx_sum16_batch.
+ * d_sum must not overlap d_seed: the host compares the two address ranges and
+ * returns LNX_EINVAL if they do.  A running sum over several calls (data that
+ * arrives in pieces) ping-pongs two arrays: call k reads as d_seed the array
+ * call k-1 wrote and writes the other, with d_phase = the bytes so far & 1.
+ * lnx_sum16_batch with d_seed = a raw sum and d_len = 0 is Sum16()
+ * (crc.go:46-49) of it: no finish entry is needed.  A payload's raw sum can be
+ * kept and reused as the seed of a rewritten header's sum (a retransmit, a
+ * rewritten address or port). */
+int lnx_sum_partial_batch(const uint8_t* d_bytes, const uint64_t* d_off, const uint32_t* d_len, const uint32_t* d_seed,
+                          const uint8_t* d_phase, uint64_t n, uint32_t* d_sum, void* stream);
+
+/* Internet checksum of frames made of segments, laid out as for
+ * lnx_crc32_chain_batch: frame f is the concatenation, in index order, of
+ * segments d_first[f] .. d_first[f+1]-1; segment k is
+ * d_bytes[d_start[k] : d_start[k] + d_len[k]]; d_first holds nframes+1 entries;
+ * a frame with d_first[f+1] <= d_first[f] has no segments; every segment index
+ * is clamped to nseg in the kernel; nseg == 0 with nframes > 0 is valid
+ * (d_bytes, d_start, d_len and d_seg_eo may then be NULL).
+ *   d_out16[f] = CRC791{d_seed ? d_seed[f] : 0}.PayloadSum16(frame f)   (crc.go:52-59),
+ *   d_sum32[f] = the raw 32-bit sum before sum16 (crc.go:17-21): lnx_sum_partial over the frame.
+ * Either output may be NULL, not both.  Segments may lie in any address order,
+ * overlap and be empty; a segment behind an odd number of bytes of its frame
+ * is summed with its bytes' weights swapped.  d_seg_eo is the caller's
+ * workspace of 2 * nseg uint32, left holding every segment's sum of even-offset
+ * bytes in [0, nseg) and of odd-offset bytes in [nseg, 2 nseg), each mod 2^32;
+ * it must not overlap an output (the host compares the ranges: LNX_EINVAL).
+ * Two launches: one that reads each segment's bytes once into d_seg_eo, then
+ * the fold of each frame's segments (12 bytes read per segment). */
+int lnx_sum16_chain_batch(const uint8_t* d_bytes, const uint64_t* d_start, const uint32_t* d_len, uint64_t nseg,
+                          const uint64_t* d_first, uint64_t nframes, const uint32_t* d_seed, uint32_t* d_seg_eo,
+                          uint16_t* d_out16, uint32_t* d_sum32, void* stream);
 
 /* Batched ethernet.CRC32Search (ethernet/crc.go:28-47), SURVEY.md §8(f).4:
  * d_result[i] = CRC32Search(d_bytes[d_off[i] : d_off[i+1]], d_min_off[i]) —

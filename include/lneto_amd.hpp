@@ -57,6 +57,8 @@ struct CRC791 {
   void AddUint16(uint16_t v) { sum += v; }
   uint16_t Sum16() const { return lnx_sum16(sum); }
   uint16_t PayloadSum16(Bytes b) const { return lnx_sum16_payload(sum, b.p, b.n); }
+  // Any length at either byte phase of the packet (lnx_sum_partial): phase = the bytes written so far & 1.
+  void WritePartial(Bytes b, int phase = 0) { sum = lnx_sum_partial(sum, b.p, b.n, phase); }
   void Reset() { sum = 0; }
 };
 
@@ -66,6 +68,22 @@ inline uint16_t NeverZeroSum(uint16_t s) { return lnx_never_zero_sum(s); }
 inline int PayloadSum16Batch(const uint8_t* d_bytes, const uint64_t* d_off, const uint32_t* d_len,
                              const uint32_t* d_seed, uint64_t n, uint16_t* d_out, void* stream = nullptr) {
   return lnx_sum16_batch(d_bytes, d_off, d_len, d_seed, n, d_out, stream);
+}
+
+// PayloadSum16 over the concatenation of m buffers (a header buffer plus a payload buffer).
+inline uint16_t PayloadSum16Chain(uint32_t seed, const uint8_t* const* seg, const size_t* len, size_t m) {
+  return lnx_sum16_chain(seed, seg, len, m);
+}
+// Batch: the raw 32-bit sums (d_sum must not overlap d_seed; d_phase: bit 0 = the segment's offset parity).
+inline int SumPartialBatch(const uint8_t* d_bytes, const uint64_t* d_off, const uint32_t* d_len, const uint32_t* d_seed,
+                           const uint8_t* d_phase, uint64_t n, uint32_t* d_sum, void* stream = nullptr) {
+  return lnx_sum_partial_batch(d_bytes, d_off, d_len, d_seed, d_phase, n, d_sum, stream);
+}
+// Batch: PayloadSum16 (d_out16) and the raw sum (d_sum32) of frames made of segments; d_segEO: 2 * nseg uint32.
+inline int PayloadSum16ChainBatch(const uint8_t* d_bytes, const uint64_t* d_start, const uint32_t* d_len, uint64_t nseg,
+                                  const uint64_t* d_first, uint64_t nframes, const uint32_t* d_seed, uint32_t* d_segEO,
+                                  uint16_t* d_out16, uint32_t* d_sum32, void* stream = nullptr) {
+  return lnx_sum16_chain_batch(d_bytes, d_start, d_len, nseg, d_first, nframes, d_seed, d_segEO, d_out16, d_sum32, stream);
 }
 
 }  // namespace lneto

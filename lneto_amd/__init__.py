@@ -22,6 +22,7 @@ __all__ = [
     "LnetoError", "lib", "crc32", "crc32_update", "crc32_search", "sum_write_even", "sum16",
     "payload_sum16", "never_zero_sum", "CRC791", "crc32_batch", "fcs_verify_batch", "sum16_batch",
     "crc32_combine", "crc32_combine_batch", "crc32_update_batch", "crc32_chain_batch", "fcs_verify_chain_batch",
+    "sum_partial", "sum16_chain", "sum_partial_batch", "sum16_chain_batch",
     "crc32_batch_host", "crc32_batch_multi", "tx_checksum_batch", "rx_verify_batch", "device_count", "version", "build_id", "LIB_PATH",
     "CRC32_RESIDUE", "RxRing", "RxFilter", "RX_NO_FCS", "research_lib",
 ]
@@ -109,6 +110,11 @@ _sig = {
     "lnx_sum16": (ctypes.c_uint16, [ctypes.c_uint32]),
     "lnx_sum16_payload": (ctypes.c_uint16, [ctypes.c_uint32, _u8p, ctypes.c_size_t]),
     "lnx_never_zero_sum": (ctypes.c_uint16, [ctypes.c_uint16]),
+    "lnx_sum_partial": (ctypes.c_uint32, [ctypes.c_uint32, _u8p, ctypes.c_size_t, ctypes.c_int]),
+    "lnx_sum16_chain": (ctypes.c_uint16, [ctypes.c_uint32, _vp, _vp, ctypes.c_size_t]),
+    "lnx_sum_partial_batch": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, ctypes.c_uint64, _vp, _vp]),
+    "lnx_sum16_chain_batch": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_uint64, _vp, ctypes.c_uint64, _vp, _vp, _vp, _vp,
+                                             _vp]),
     "lnx_crc32_batch": (ctypes.c_int, [_vp, _vp, ctypes.c_uint64, _vp, _vp]),
     "lnx_fcs_verify_batch": (ctypes.c_int, [_vp, _vp, ctypes.c_uint64, _vp, _vp]),
     "lnx_sum16_batch": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_uint64, _vp, _vp]),
@@ -212,6 +218,24 @@ def payload_sum16(s: int, p: bytes) -> int:
 
 def never_zero_sum(x: int) -> int:
     return lib.lnx_never_zero_sum(x & 0xFFFF)
+
+
+def sum_partial(s: int, p: bytes, phase: int = 0) -> int:
+    """The raw 32-bit running sum of CRC791 over a piece of a packet (lnx_sum_partial):
+    any length; phase = the parity of the piece's offset in its packet.
+    sum16(sum_partial(s, p)) == payload_sum16(s, p)."""
+    b, n = _buf(p)
+    return lib.lnx_sum_partial(s & 0xFFFFFFFF, b, n, phase & 1)
+
+
+def sum16_chain(seed: int, segs) -> int:
+    """CRC791{seed}.PayloadSum16 over the concatenation of the buffers in ``segs`` (lnx_sum16_chain)."""
+    segs = [bytes(g) for g in segs]
+    m = len(segs)
+    bufs = [_buf(g)[0] for g in segs]  # kept alive until the call returns
+    ptrs = (ctypes.c_void_p * max(m, 1))(*[ctypes.addressof(b) for b in bufs])
+    lens = (ctypes.c_size_t * max(m, 1))(*[len(g) for g in segs])
+    return lib.lnx_sum16_chain(seed & 0xFFFFFFFF, ctypes.addressof(ptrs), ctypes.addressof(lens), m)
 
 
 class CRC791:
@@ -422,7 +446,7 @@ def crc32_update_batch(d_bytes, d_off, d_seed=None, out=None, stream=None):
     return out
 
 
-def _chain_args(what, d_bytes, d_start, d_len, d_first, d_seed, seg_crc, nseg, stream):
+def _chain_args(what, d_bytes, d_start, d_len, d_first, d_seed, seg_crc, nseg, stream, ws_per_seg=1):
     import torch
     b = _Batch(what, [("d_bytes", d_bytes, "u8"), ("d_start", d_start, "i64"), ("d_len", d_len, "i32"),
                       ("d_first", d_first, "i64"), ("d_seed", d_seed, "i32?")], stream)
@@ -433,7 +457,7 @@ def _chain_args(what, d_bytes, d_start, d_len, d_first, d_seed, seg_crc, nseg, s
     _need_len(what, "d_len", d_len, nseg)
     _need_len(what, "d_seed", d_seed, nframes)
     # the library allocates nothing: the workspace is made here when the caller passes none
-    seg_crc = _out(what, seg_crc, nseg, torch.int32, "i32", b.device)
+    seg_crc = _out(what, seg_crc, ws_per_seg * nseg, torch.int32, "i32", b.device)
     return b, nseg, nframes, seg_crc
 
 
@@ -639,6 +663,57 @@ def sum16_batch(d_bytes, d_off, d_len, d_seed=None, out=None, stream=None):
                                        d_seed.data_ptr() if d_seed is not None else None, n,
                                        out.data_ptr(), s), what)
     return out
+
+
+def sum_partial_batch(d_bytes, d_off, d_len, d_seed=None, d_phase=None, out=None, stream=None):
+    """The raw 32-bit running sums of N segments on the GPU (lnx_sum_partial_batch):
+    out[i] = sum_partial(d_seed[i] or 0, d_bytes[off[i]:off[i]+len[i]], d_phase[i] or 0).
+
+    d_off: int64 (N), d_len: int32 (N), d_seed: int32 (N) or None, d_phase: uint8
+    (N, bit 0 read) or None.  ``out`` must not overlap d_seed; a running sum over
+    several calls ping-pongs two arrays.  sum16_batch with d_seed = a raw sum and
+    zero lengths is Sum16() of it.  Returns int32 (uint32 bits)."""
+    import torch
+    what = "lnx_sum_partial_batch"
+    b = _Batch(what, [("d_bytes", d_bytes, "u8"), ("d_off", d_off, "i64"), ("d_len", d_len, "i32"),
+                      ("d_seed", d_seed, "i32?"), ("d_phase", d_phase, "u8?")], stream)
+    n = d_off.numel()
+    _need_len(what, "d_len", d_len, n)
+    _need_len(what, "d_seed", d_seed, n)
+    _need_len(what, "d_phase", d_phase, n)
+    out = _out(what, out, n, torch.int32, "i32", b.device)
+    if n > 0:
+        with b as s:
+            _check(lib.lnx_sum_partial_batch(d_bytes.data_ptr(), d_off.data_ptr(), d_len.data_ptr(), _ptr(d_seed),
+                                             _ptr(d_phase), n, out.data_ptr(), s), what)
+    return out
+
+
+def sum16_chain_batch(d_bytes, d_start, d_len, d_first, d_seed=None, out16=True, sum32=False, seg_eo=None, nseg=None,
+                      stream=None):
+    """Internet checksum of frames made of segments (lnx_sum16_chain_batch; the
+    layout of crc32_chain_batch): out16[f] = CRC791{d_seed[f] or 0}.PayloadSum16(
+    frame f), sum32[f] = the raw 32-bit sum before the fold.  ``out16`` /
+    ``sum32``: a tensor (int16 / int32, nframes) to write, True to allocate one,
+    False for none (NULL in the C-ABI; not both).  ``seg_eo`` (int32, 2 * nseg)
+    is the workspace, allocated when None and left holding every segment's sum
+    of even-offset bytes in [0, nseg) and of odd-offset bytes in [nseg, 2 nseg).
+    Returns (out16 or None, sum32 or None)."""
+    import torch
+    what = "lnx_sum16_chain_batch"
+    if (out16 is False or out16 is None) and (sum32 is False or sum32 is None):
+        raise LnetoError(f"{what}: one of out16 and sum32 is required")
+    b, nseg, nframes, seg_eo = _chain_args(what, d_bytes, d_start, d_len, d_first, d_seed, seg_eo, nseg, stream, 2)
+    o16 = None if out16 is False or out16 is None else _out(what, None if out16 is True else out16, nframes,
+                                                             torch.int16, "i16", b.device)
+    s32 = None if sum32 is False or sum32 is None else _out(what, None if sum32 is True else sum32, nframes,
+                                                             torch.int32, "i32", b.device)
+    if nframes > 0:
+        with b as s:
+            _check(lib.lnx_sum16_chain_batch(d_bytes.data_ptr(), d_start.data_ptr(), d_len.data_ptr(), nseg,
+                                             d_first.data_ptr(), nframes, _ptr(d_seed), seg_eo.data_ptr(), _ptr(o16),
+                                             _ptr(s32), s), what)
+    return o16, s32
 
 
 def crc32_batch_multi(parts, devices):

@@ -27,6 +27,16 @@ hipError_t launch_chain_fold(const uint32_t* seg_crc, const uint32_t* len, uint6
                              hipStream_t stream);
 }  // namespace lnxc
 
+// sum16_chain_kernel.hip: the running internet checksums
+namespace lnxs {
+hipError_t launch_sum_bytes(const uint8_t* bytes, const uint64_t* off, const uint32_t* len, const uint32_t* seed,
+                            const uint8_t* phase, uint64_t n, uint32_t* out, bool planes, int num_cus,
+                            hipStream_t stream);
+hipError_t launch_sum_fold(const uint32_t* eo, const uint32_t* len, uint64_t nseg, const uint64_t* first,
+                           uint64_t nframes, const uint32_t* seed, uint16_t* out16, uint32_t* sum32, int num_cus,
+                           hipStream_t stream);
+}  // namespace lnxs
+
 namespace lnx {
 hipError_t launch_crc32_frames(const uint8_t* bytes, const uint64_t* off, uint64_t n, void* out,
                                bool verify, const void* image, int num_cus, hipStream_t stream, uint32_t policy,
@@ -685,6 +695,49 @@ int lnx_fcs_verify_chain_batch(const uint8_t* d_bytes, const uint64_t* d_start, 
   return chain_common(d_bytes, d_start, d_len, nseg, d_first, nframes, nullptr, d_seg_crc, d_ok, true, stream);
 }
 
+// Two address ranges of a and b bytes share a byte.
+static bool ranges_overlap(const void* pa, uint64_t a, const void* pb, uint64_t b) {
+  const uintptr_t x = reinterpret_cast<uintptr_t>(pa), y = reinterpret_cast<uintptr_t>(pb);
+  return a && b && x < y + b && y < x + a;
+}
+
+int lnx_sum_partial_batch(const uint8_t* d_bytes, const uint64_t* d_off, const uint32_t* d_len, const uint32_t* d_seed,
+                          const uint8_t* d_phase, uint64_t n, uint32_t* d_sum, void* stream) {
+  if (n == 0) return LNX_OK;
+  if (!d_bytes || !d_off || !d_len || !d_sum) return LNX_EINVAL;
+  // a row reads seed[i] and writes sum[i]; another row's seed must not have been written yet
+  if (d_seed && ranges_overlap(d_seed, n * sizeof(uint32_t), d_sum, n * sizeof(uint32_t))) return LNX_EINVAL;
+  DeviceCtx* c = nullptr;
+  int st = get_ctx(&c);
+  if (st != LNX_OK) return st;
+  const hipError_t e = lnxs::launch_sum_bytes(d_bytes, d_off, d_len, d_seed, d_phase, n, d_sum, false, c->num_cus,
+                                              static_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return hip_fail(e, "sum_bytes_kernel (partial) launch");
+  return LNX_OK;
+}
+
+int lnx_sum16_chain_batch(const uint8_t* d_bytes, const uint64_t* d_start, const uint32_t* d_len, uint64_t nseg,
+                          const uint64_t* d_first, uint64_t nframes, const uint32_t* d_seed, uint32_t* d_seg_eo,
+                          uint16_t* d_out16, uint32_t* d_sum32, void* stream) {
+  if (nframes == 0) return LNX_OK;
+  if (!d_first || (!d_out16 && !d_sum32)) return LNX_EINVAL;
+  if (nseg > 0 && (!d_bytes || !d_start || !d_len || !d_seg_eo)) return LNX_EINVAL;
+  // the fold reads the planes while it writes the outputs
+  const uint64_t ws = 2 * nseg * sizeof(uint32_t);
+  if (nseg > 0 && ((d_out16 && ranges_overlap(d_seg_eo, ws, d_out16, nframes * sizeof(uint16_t))) ||
+                   (d_sum32 && ranges_overlap(d_seg_eo, ws, d_sum32, nframes * sizeof(uint32_t)))))
+    return LNX_EINVAL;
+  DeviceCtx* c = nullptr;
+  int st = get_ctx(&c);
+  if (st != LNX_OK) return st;
+  const hipStream_t hs = static_cast<hipStream_t>(stream);
+  hipError_t e = lnxs::launch_sum_bytes(d_bytes, d_start, d_len, nullptr, nullptr, nseg, d_seg_eo, true, c->num_cus, hs);
+  if (e != hipSuccess) return hip_fail(e, "sum_bytes_kernel (planes) launch");
+  e = lnxs::launch_sum_fold(d_seg_eo, d_len, nseg, d_first, nframes, d_seed, d_out16, d_sum32, c->num_cus, hs);
+  if (e != hipSuccess) return hip_fail(e, "sum_fold_kernel launch");
+  return LNX_OK;
+}
+
 int lnx_fcs_append_batch(uint8_t* d_bytes, const uint64_t* d_start, uint32_t* d_len, uint64_t n, uint32_t capacity,
                          uint8_t* d_status, void* stream) {
   if (n == 0) return LNX_OK;
@@ -991,7 +1044,7 @@ int lnx_device_count(void) {
 const char* lnx_last_error(void) { return g_last_error.c_str(); }
 
 const char* lnx_version(void) {
-  return "lneto_amd 0.12 gfx950: crc32 rows (32-lane whole-line rows from 4096 B mean: 24-line items; one-word "
+  return "lneto_amd 0.13 gfx950: crc32 rows (32-lane whole-line rows from 4096 B mean: 24-line items; one-word "
          "16-lane rows 1600-4096 B: 1 slot x 24 steps, 4-frame chunks; lean two-word line rows 640-1600 B, offsets "
          "and segment mode: one 13-line frame per row per slot; whole-line rows load a frame's first and last lines "
          "at the default cache policy, the rest nt; 4-lane rows: 2 slots x 16 steps, 32-frame chunks, held results; "
@@ -1008,7 +1061,8 @@ const char* lnx_version(void) {
          "skipped) + tx_finish (checksums, padding and FCS in one read, CRC corrected by linearity; 16 waves, "
          "48-frame groups) + zero copy through the ring's pinned slots + running CRCs (seeds, "
          "combine, frames made of segments: Z_k by nibble tables of x^(8 * 2^j) in LDS, a 16-lane row or the "
-         "workgroup per frame)";
+         "workgroup per frame) + running internet checksums (raw 32-bit sums at either byte phase, frames made of "
+         "segments: the sum16 line rows into E / O planes, a 16-lane row or the workgroup's four waves per frame)";
 }
 
 }  // extern "C"
