@@ -551,3 +551,203 @@ def limit_frames(seed: int = 65535) -> list[tuple[str, bytes]]:
     for kind, z in zero_udp:
         out.append((f"tx/{kind}/65535/sum_zero", _limit_garble(z, kind, rng)))
     return out
+
+
+# ------------------------------------------------ IPv4 options in front of every transport
+OPT_L4 = ("tcp", "udp", "echo", "reply", "icmp3", "p47")   # ICMP echo (type 8), echo reply (0), type 3; protocol 47
+OPT_FILLS = ("rand", "ramp", "first", "last")              # the discriminating fills; "ff" beside them for carries
+OPT_LENGTHS = (0, 1, 2, 3, 7, 8, 9, 17, 18, 19, 64, 65, 200, 1401)  # transport payload bytes; 4000 once per (IHL, L4)
+OPT_VARIANT_LENGTHS = (0, 1, 9, 18, 65, 1401)              # the lengths the variants are crossed with
+OPT_PROTO = {"tcp": 6, "udp": 17, "echo": 1, "reply": 1, "icmp3": 1, "p47": 47}
+
+
+def opt_fill(fill: str, n: int, rng) -> bytes:
+    """n option bytes (n = 4 (IHL - 5)).  rand: bytes 1..255; ramp: a non-zero
+    ramp; first / last: only that byte non-zero; ff: all 0xFF (carries only: a
+    0xFFFF word is one's-complement zero).  rand and ramp are redrawn until
+    the options' 16-bit words do not sum to a multiple of 0xFFFF, so that a sum
+    which wrongly covers them always differs."""
+    if n == 0:
+        return b""
+    while True:
+        if fill == "rand":
+            b = rng.integers(1, 256, n, dtype=np.uint8).tobytes()
+        elif fill == "ramp":
+            k = int(rng.integers(0, 255))
+            b = bytes(1 + (k + 7 * i) % 255 for i in range(n))
+        elif fill == "first":
+            b = bytes([int(rng.integers(1, 256))]) + bytes(n - 1)
+        elif fill == "last":
+            b = bytes(n - 1) + bytes([int(rng.integers(1, 256))])
+        elif fill == "ff":
+            return b"\xff" * n
+        else:
+            raise ValueError(fill)
+        if O.sum_write_even(0, b) % 0xFFFF != 0:
+            return b
+
+
+def _opt_l4(l4: str, pay: bytes) -> bytes:
+    if l4 == "tcp":
+        return tcp(pay)
+    if l4 == "udp":
+        return udp(pay)
+    if l4 == "p47":
+        return pay
+    return icmp({"echo": 8, "reply": 0, "icmp3": 3}[l4], pay)
+
+
+def _refix_header(b: bytearray) -> None:
+    b[24:26] = b"\0\0"
+    b[24:26] = struct.pack(">H", O.ipv4_header_sum16(bytes(b[14:34])))
+
+
+def ip4_option_frames(seed: int = 4015) -> list[tuple[str, bytes]]:
+    """(label, frame) pairs with NON-ZERO IPv4 options in front of every transport
+    the checksum kernels know.  The header sum covers 20 bytes whatever the IHL
+    (ipv4/frame.go:144-146) and the transport segment starts at 14 + 4 IHL, so
+    the option bytes belong to neither sum.  Deterministic.
+
+    rx/<l4>/ihl<k>/<fill>/<n>/valid: OPT_L4 x IHL 5..15 x OPT_FILLS and "ff" x
+      OPT_LENGTHS (n transport payload bytes), and n = 4000 once per (IHL, L4).
+    rx/<l4>/ihl<k>/<fill>/<n>/<variant>: OPT_L4 x IHL x OPT_VARIANT_LENGTHS, the
+      fills of OPT_FILLS in rotation, with
+        optflip (one option byte changed: verdict and pcap status as `valid`),
+        l4flip, srcflip (pseudo-header), ttl (header sum), ttl+l4flip, trail
+        (non-zero bytes past tl), runt (zero-padded to 60 bytes), cut1 (last
+        byte missing), cutopt (the frame ends inside the options), tl=hl-1,
+        tl=hl (header sum redone), ver5, evil (header sum redone);
+        UDP: ulen7, ulenP+1, ulenP+1+ttl, ulen_short (a UDP length below the IP
+        payload, non-zero bytes after it), csum0 (checksum field 0);
+        TCP: doff4, doff4+ttl, doff15 (the TCP checksum is valid).
+    tx/<l4>/ihl<k>/<fill>/<n>/stale: every valid frame of a fill in OPT_FILLS
+      with random bytes in the total length, the header CRC, the transport
+      checksum and the UDP length.
+    tx/udp/ihl<k>/<fill>/18/zero_sum: a UDP datagram behind options whose
+      checksum computes to 0 (NeverZeroSum stores 0xFFFF), the field stale.
+    tx/<l4>/ihl<k>/...: IHL 0..4 (ihl_low), a frame that ends inside the
+      options (cutopt), a transport header too short (short_l4)."""
+    rng = np.random.default_rng(seed)
+    out = []
+
+    def payload(n):
+        return rng.integers(0, 256, n, dtype=np.uint8).tobytes()
+
+    def base(l4, ihl, fill, n, fix=True, evil=False, pay=None):
+        opts = opt_fill(fill, 4 * (ihl - 5), rng)
+        body = _opt_l4(l4, payload(n) if pay is None else pay)
+        return ether(0x0800, ipv4(OPT_PROTO[l4], body, opts=opts, flags=0x2000 if evil else 0x4000, fix_l4=fix))
+
+    def stale(f, l4, ihl):
+        b = bytearray(f)
+        la = 14 + 4 * ihl
+        at = [16, 24] + {"tcp": [la + 16], "udp": [la + 4, la + 6], "p47": []}.get(l4, [la + 2])
+        for o in at:
+            if o + 2 <= len(b):
+                b[o:o + 2] = rng.integers(0, 256, 2, dtype=np.uint8).tobytes()
+        return bytes(b)
+
+    # ---- the valid matrix and its transmit form
+    for l4 in OPT_L4:
+        for ihl in range(5, 16):
+            for fill in OPT_FILLS + ("ff",):
+                for n in OPT_LENGTHS + ((4000,) if fill == "rand" else ()):
+                    f = base(l4, ihl, fill, n)
+                    out.append((f"rx/{l4}/ihl{ihl}/{fill}/{n}/valid", f))
+                    if fill != "ff":
+                        out.append((f"tx/{l4}/ihl{ihl}/{fill}/{n}/stale", stale(f, l4, ihl)))
+
+    # ---- the receive variants
+    rot = 0
+    for l4 in OPT_L4:
+        hdr = {"tcp": 20, "udp": 8, "p47": 0}.get(l4, 8)
+        for ihl in range(5, 16):
+            hl, la = 4 * ihl, 14 + 4 * ihl
+            for n in OPT_VARIANT_LENGTHS:
+                fill = OPT_FILLS[rot % len(OPT_FILLS)]
+                rot += 1
+                f = base(l4, ihl, fill, n)
+                tag = f"rx/{l4}/ihl{ihl}/{fill}/{n}/"
+
+                def put(name, b):
+                    out.append((tag + name, bytes(b)))
+
+                if ihl > 5:  # the first, the last or any option byte (the last lies past the staged bytes at IHL 13-15)
+                    b = bytearray(f)
+                    at = [34, la - 1, int(rng.integers(34, la))][rot % 3]
+                    b[at] ^= 1 << int(rng.integers(0, 8))
+                    put("optflip", b)
+                    put("cutopt", f[:int(rng.integers(35, la))])
+                if hdr + n > 0:
+                    b = bytearray(f)
+                    b[int(rng.integers(la, len(b)))] ^= 1 << int(rng.integers(0, 8))
+                    put("l4flip", b)
+                    b[22] ^= 0x01
+                    put("ttl+l4flip", b)
+                b = bytearray(f)
+                b[int(rng.integers(26, 30))] ^= 1 << int(rng.integers(0, 8))
+                put("srcflip", b)
+                b = bytearray(f)
+                b[22] ^= 0x01
+                put("ttl", b)
+                put("trail", f + rng.integers(1, 256, int(rng.integers(1, 31)), dtype=np.uint8).tobytes())
+                if len(f) < 60:
+                    put("runt", f + bytes(60 - len(f)))
+                put("cut1", f[:-1])
+                for name, tl in (("tl=hl-1", hl - 1), ("tl=hl", hl)):
+                    b = bytearray(f)
+                    b[16:18] = struct.pack(">H", tl)
+                    _refix_header(b)
+                    put(name, b)
+                b = bytearray(f)
+                b[14] = 0x50 | ihl
+                put("ver5", b)
+                put("evil", base(l4, ihl, fill, n, evil=True))
+                if l4 == "udp":
+                    for name, ul in (("ulen7", 7), ("ulenP+1", 8 + n + 1)):
+                        b = bytearray(f)
+                        b[la + 4:la + 6] = struct.pack(">H", ul)
+                        put(name, b)
+                    b[22] ^= 0x01
+                    put("ulenP+1+ttl", b)
+                    if n >= 1:  # the checksum covers ul bytes; what follows them is non-zero and outside it
+                        ul = 8 + int(rng.integers(0, n))
+                        pay = rng.integers(1, 256, n, dtype=np.uint8).tobytes()
+                        opts = opt_fill(fill, 4 * (ihl - 5), rng)
+                        put("ulen_short", ether(0x0800, ipv4(17, udp(pay, length=ul), opts=opts)))
+                    b = bytearray(f)
+                    b[la + 6:la + 8] = b"\0\0"
+                    put("csum0", b)
+                if l4 == "tcp":
+                    for name, doff in (("doff4", 4), ("doff15", 15)):
+                        seg = bytearray(tcp(payload(n)))
+                        seg[12] = doff << 4
+                        b = bytearray(ether(0x0800, ipv4(6, bytes(seg), opts=opt_fill(fill, 4 * (ihl - 5), rng))))
+                        put(name, b)
+                        if doff == 4:
+                            b[22] ^= 0x01
+                            put("doff4+ttl", b)
+
+    # ---- the transmit forms that are no valid frame
+    for ihl in range(5, 16):
+        fill = OPT_FILLS[ihl % len(OPT_FILLS)]
+        opts = opt_fill(fill, 4 * (ihl - 5), rng)
+        la = 14 + 4 * ihl
+        f = bytearray(ether(0x0800, ipv4(17, udp(payload(16) + bytes(2)), opts=opts, fix_l4=False)))
+        g, st = O.tx_checksum(bytes(f))
+        assert st == 0
+        f[-2:] = g[la + 6:la + 8]          # the sum now computes to 0
+        f[la + 6:la + 8] = b"\x12\x34"     # and the field is stale
+        out.append((f"tx/udp/ihl{ihl}/{fill}/18/zero_sum", bytes(f)))
+        for l4 in ("tcp", "udp", "echo"):
+            f = stale(base(l4, ihl, fill, 33, fix=False), l4, ihl)
+            if ihl > 5:
+                out.append((f"tx/{l4}/ihl{ihl}/{fill}/33/cutopt", f[:int(rng.integers(35, la))]))
+            short = {"tcp": 20, "udp": 8, "echo": 8}[l4]
+            out.append((f"tx/{l4}/ihl{ihl}/{fill}/33/short_l4", f[:la + int(rng.integers(0, short))]))
+    for low in range(5):
+        for l4 in ("tcp", "udp", "echo"):
+            b = bytearray(stale(base(l4, 7, "rand", 40, fix=False), l4, 7))
+            b[14] = 0x40 | low
+            out.append((f"tx/{l4}/ihl{low}/rand/40/ihl_low", bytes(b)))
+    return out
