@@ -25,8 +25,12 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include "gf2.hpp"
+#include "wave_util.hpp"
 
 namespace lnxc {
+
+using lnx::row_xor16;
+using lnx::uniform64;
 
 constexpr int kZLevels = 64;              // bits of a length
 constexpr int kZDwords = kZLevels * 128;  // eight 16-entry nibble tables per level: 32 KiB
@@ -81,20 +85,13 @@ __device__ __forceinline__ void load_zimage(uint32_t* zt) {
   __syncthreads();
 }
 
-// OR / XOR over each 16-lane row, the result in every lane of the row (the DPP
-// chain of sum16's row_add16).
+// OR over each 16-lane row, the result in every lane of the row (the DPP
+// chain of wave_util.hpp's row_xor16).
 __device__ __forceinline__ uint32_t row_or16(uint32_t v) {
   v |= (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xB1, 0xF, 0xF, false);   // quad_perm [1,0,3,2]
   v |= (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x4E, 0xF, 0xF, false);   // quad_perm [2,3,0,1]
   v |= (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x124, 0xF, 0xF, false);  // row_ror:4
   v |= (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x128, 0xF, 0xF, false);  // row_ror:8
-  return v;
-}
-__device__ __forceinline__ uint32_t row_xor16(uint32_t v) {
-  v ^= (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xB1, 0xF, 0xF, false);
-  v ^= (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x4E, 0xF, 0xF, false);
-  v ^= (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x124, 0xF, 0xF, false);
-  v ^= (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x128, 0xF, 0xF, false);
   return v;
 }
 // The four rows' values joined in scalar registers (wave-uniform).
@@ -107,13 +104,6 @@ __device__ __forceinline__ uint32_t wave_xor(uint32_t v) {
   v = row_xor16(v);
   return (uint32_t)(__builtin_amdgcn_readlane((int)v, 0) ^ __builtin_amdgcn_readlane((int)v, 16) ^
                     __builtin_amdgcn_readlane((int)v, 32) ^ __builtin_amdgcn_readlane((int)v, 48));
-}
-
-// A value every lane holds alike, moved to scalar registers so that the
-// branches and loop bounds taken from it are scalar too.
-__device__ __forceinline__ uint64_t uniform64(uint64_t v) {
-  return (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v) |
-         ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32)) << 32);
 }
 
 // Z_{2^j}(r), zl = the level's eight nibble tables.

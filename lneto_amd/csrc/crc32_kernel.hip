@@ -48,6 +48,7 @@
 #include <utility>
 #include "lds_layout.hpp"
 #include "dispatch.hpp"
+#include "wave_util.hpp"
 
 // Cache-policy suffix of the streaming frame loads (e.g. " nt" for profiling
 // builds: make CXXFLAGS+='-DLNX_LD_POL=\"\ nt\"').  Default policy by default.
@@ -155,12 +156,6 @@ __device__ __forceinline__ uint32_t t_fix(const char* lds, uint32_t R, uint32_t 
     a = dpp_xor<kQuadX1>(a);
     return dpp_xor<kQuadX2>(a);
   }
-}
-
-// Bytes [lo, 4) of a little-endian word kept (lo clamped to 0..4).
-__device__ __forceinline__ uint32_t keep_from(int32_t lo) {
-  lo = lo < 0 ? 0 : (lo > 4 ? 4 : lo);
-  return (uint32_t)(0xFFFFFFFFull << (8 * lo));
 }
 
 __device__ __forceinline__ bool wave_any(bool b) { return __builtin_amdgcn_ballot_w64(b) != 0; }
@@ -1244,10 +1239,6 @@ __device__ __forceinline__ void lines_body(const char* lds, const Lanes& L, cons
     // step 0: the lane's 8 bytes keep [lead - 8p, 8) and take the init 0xFF
     // over [lead - 8p, lead - 8p + m4); bytes [d, 8) of a qword are
     // (~0 << 4d) << 4d for d in 0..8 (two shifts: a 64-bit shift by 64 is 0)
-    auto keep8 = [](int32_t d) -> uint64_t {
-      const uint32_t q = 4u * (uint32_t)(d < 0 ? 0 : (d > 8 ? 8 : d));
-      return (~0ull << q) << q;
-    };
     const int32_t d0 = (int32_t)lead - (int32_t)(p * 4u * WL);
     Word w0;
     if constexpr (WL == 2) {

@@ -2,24 +2,8 @@
 // (SURVEY.md §8(f).2).
 //
 // For every received Ethernet frame (FCS stripped) the verdict lneto's receive
-// path reaches at its checksum stage, as one kernel:
-//   StackEthernet.Demux size checks (internet/stack-ethernet.go:139-165,
-//   ethernet/frame.go:13-18,119-127), then by EtherType
-//   0x0800 demux4 (internet/stack-ip4.go:100-164): ipv4.NewFrame, the first
-//          error of ValidateExceptCRC (ipv4/frame.go:214-238), the header sum
-//          over the first 20 bytes only (ipv4/frame.go:138-146), TCP / UDP
-//          checksums with the pseudo-header seeds (ipv4/frame.go:154-170) and
-//          the UDP size checks (udp/frame.go:15-20,96-104);
-//   0x86DD demux6 (internet/stack-ip6.go:86-138): ipv6.NewFrame, ValidateSize
-//          (ipv6/frame.go:123-128), TCP / UDP sums with CRCWritePseudo
-//          (ipv6/frame.go:104-108); the UDP sum covers the whole IPv6 payload;
-//   with kVerifyIcmp, ICMP messages also take their client's Demux checks up to
-//          the checksum (ipv4/icmpv4/client.go:89-102: size, echo types,
-//          sum with no pseudo-header; ipv6/icmpv6/client.go:100-115: size,
-//          sum with the pseudo-header, as CRCWritePseudo with proto 58).
-// The verdict is 0 (every check passed, or none applies) or the errGeneric
-// code the reference returns (errors.go:6-28).  Destination filtering and
-// handler lookup depend on stack configuration: taken as accept-all.
+// path reaches at its checksum stage, as one kernel: the rules (rx_plan) and
+// the reference lines they restate are in frame_plan.hpp.
 //
 // Layout: one 16-lane row per frame, four frames per wave.  The row's first
 // batch of dword loads (frame offsets from 12 on) also carries every header
@@ -35,7 +19,9 @@
 #include <cstdint>
 #include <cstdlib>
 #include <type_traits>
+#include "frame_plan.hpp"
 #include "rx_filter.hpp"
+#include "wave_util.hpp"
 
 namespace lnx {
 
@@ -46,55 +32,16 @@ constexpr int kIngBlock = 256;
 [[maybe_unused]] constexpr int kIngUnroll = 24;
 // qword lanes (r1h product): 12 qwords per lane in flight, again 1536 B per row
 constexpr int kIngUnrollQ = 12;
-constexpr uint32_t kErrPacketDrop = 2, kErrBadCRC = 3, kErrInvalidField = 14, kErrInvalidLengthField = 15,
-                   kErrTruncatedFrame = 18;
-constexpr uint32_t kVerifyEvilBit = 1, kVerifyIcmp = 2;
-
-// bit `proto` of a 256-bit mask held in kernel-argument words (a select chain:
-// no indexed scratch)
-__device__ __forceinline__ bool proto_bit(const uint32_t (&m)[8], uint32_t proto) {
-  const uint32_t w = proto >> 5;
-  const uint32_t word = w == 0 ? m[0] : w == 1 ? m[1] : w == 2 ? m[2] : w == 3 ? m[3] : w == 4 ? m[4]
-                        : w == 5 ? m[5] : w == 6 ? m[6] : m[7];
-  return (word >> (proto & 31u)) & 1u;
-}
-
-__device__ __forceinline__ uint32_t ing_keep_from(int32_t lo) {
-  lo = lo < 0 ? 0 : (lo > 4 ? 4 : lo);
-  return (uint32_t)(0xFFFFFFFFull << (8 * lo));
-}
-// byte mask of the frame offsets [a, b) inside the word whose byte 0 is at o0
-__device__ __forceinline__ uint32_t range_mask(int32_t o0, int32_t a, int32_t b) {
-  return ing_keep_from(a - o0) & ~ing_keep_from(b - o0);
-}
-
-__device__ __forceinline__ uint32_t row_add(uint32_t v) {
-  v += (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xB1, 0xF, 0xF, false);   // quad_perm [1,0,3,2]
-  v += (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x4E, 0xF, 0xF, false);   // quad_perm [2,3,0,1]
-  v += (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x124, 0xF, 0xF, false);  // row_ror:4
-  v += (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x128, 0xF, 0xF, false);  // row_ror:8
-  return v;
-}
-
-__device__ __forceinline__ uint16_t ing_sum16(uint32_t sum) {  // crc.go:17-21
-  sum = (sum & 0xffffu) + (sum >> 16);
-  return (uint16_t)~(uint16_t)(sum + (sum >> 16));
-}
 
 // QW: lanes load qwords (global_load_dwordx2: a 16-lane row reads a whole
 // 128-byte line per instruction), UNR qwords per lane in flight; otherwise
 // dwords (a 64-byte half line per row instruction), UNR dwords in flight
 //
 // GEN (tx_checksum_batch): the same rows GENERATE the
-// checksums instead (encapsulate4 / encapsulate6 / the ICMP clients after the
-// child wrote its n payload bytes, internet/stack-ip4.go:202-228,
-// internet/stack-ip6.go:167-181, ipv4/icmpv4/client.go:210-214,
-// ipv6/icmpv6/client.go:135-148): the length fields are set from the frame
-// length, and the sums are taken over the bytes as loaded with the old field
-// values subtracted (uint32 wrap: the same value as summing with the fields
-// zeroed); lanes 0..7 of the row then store the 2-byte fields (IPv4 total
-// length / IPv6 payload length, header CRC, transport CRC, UDP length) and
-// `verdict` receives the status (0, or 18 / 15 with the frame untouched).
+// checksums instead (the tree below, after oracle.tx_checksum); lanes 0..3 of the row then
+// store the 2-byte fields (IPv4 total length / IPv6 payload length, header
+// CRC, transport CRC, UDP length) and `verdict` receives the status (0, or
+// 18 / 15 with the frame untouched).
 // (the generate form writes the frames: its byte pointer is not const)
 template <bool GEN>
 using IngBytes = std::conditional_t<GEN, uint8_t, const uint8_t>;
@@ -199,21 +146,23 @@ ingress_verify_kernel(IngBytes<GEN>* __restrict__ bytes, const uint64_t* __restr
       return ((v2 & 0xFFu) << 8) | ((v2 >> 8) & 0xFFu);
     };
 
-    // ---- header parse: row-uniform; v = verdict so far, sums requested below
+    // ---- header parse (frame_plan.hpp): row-uniform, every lane of the row
+    // gathers the same fields; offsets below 24 sit in H0..H2, the rest come
+    // through field16 / field32
+    auto hword = [&](int o) -> uint32_t { return o < 16 ? H0 : o < 20 ? H1 : H2; };
+    auto be16 = [&](int o) -> uint32_t { return o < 24 ? be(hword(o), o & 3) : field16((uint32_t)o); };
+    auto byte_at = [&](int o) -> uint32_t { return byt(hword(o), o & 3); };
     uint32_t v = 0;
-    uint32_t v_udp4 = 0;  // IPv4 UDP / ICMP size verdict: demux4 reports it only after the header sum passed
     bool hdr_sum = false, l4_sum = false;
     int32_t pa = 0, pb = 0, la = 0, lb = 0;  // pseudo-address bytes [pa, pb), transport [la, lb)
     uint32_t lseed = 0;                       // length + protocol words of the pseudo-header
-    // A 16-bit big-endian field value v at an even frame offset adds cv(v) to
-    // the qword rows' little-endian half-word sum S (see the sums below): its
-    // high byte sits at address parity mis & 1
-    auto cv = [&](uint32_t v) -> uint32_t { return (mis & 1u) ? v : (((v & 0xFFu) << 8) | (v >> 8)); };
+    [[maybe_unused]] RxPlan rx;
     // GEN: the fields the step writes (frame offset, new value; 0 = none)
     uint32_t g_off[4] = {0, 0, 0, 0}, g_val[4] = {0, 0, 0, 0};
     uint32_t g_fix_h = 0, g_fix_t = 0;  // cv(new) - cv(old) of the summed fields (header, transport), mod 2^32
     bool g_nz = false;                   // UDP: NeverZeroSum (crc.go:65-71)
     if constexpr (GEN) {
+      // (inline, as tx_finish_kernel's copy in rx_verify_kernel.hip: see the note there)
       if (L < 14) {
         v = kErrTruncatedFrame;
       } else {
@@ -232,17 +181,17 @@ ingress_verify_kernel(IngBytes<GEN>* __restrict__ bytes, const uint64_t* __restr
               hdr_sum = true;
               g_off[0] = 16, g_val[0] = tl;   // SetTotalLength(n + hl)
               g_off[1] = 24;                  // SetCRC(CalculateHeaderCRC()), value after the sums
-              g_fix_h = cv(tl) - cv(be(H1, 0)) - cv(field16(24));
+              g_fix_h = cv(mis, tl) - cv(mis, be(H1, 0)) - cv(mis, field16(24));
               if (need) {
                 l4_sum = true;
                 la = 14 + hl, lb = L;
                 const uint32_t at = proto == 6 ? 16u : proto == 17 ? 6u : 2u;
                 g_off[2] = la + at;
-                g_fix_t = 0u - cv(field16(la + at));
+                g_fix_t = 0u - cv(mis, field16(la + at));
                 if (proto != 1) pa = 26, pb = 34, lseed = nn + proto;  // CRCWriteTCPPseudo / CRCWriteUDPPseudo(n)
                 if (proto == 17) {
                   g_off[3] = la + 4, g_val[3] = nn;  // SetLength(n)
-                  g_fix_t += cv(nn) - cv(field16(la + 4));
+                  g_fix_t += cv(mis, nn) - cv(mis, field16(la + 4));
                   g_nz = true;
                 }
               }
@@ -262,10 +211,10 @@ ingress_verify_kernel(IngBytes<GEN>* __restrict__ bytes, const uint64_t* __restr
               lseed = nn + proto;
               const uint32_t at = proto == 6 ? 16u : proto == 17 ? 6u : 2u;
               g_off[2] = 54 + at;
-              g_fix_t = 0u - cv(field16(54 + at));
+              g_fix_t = 0u - cv(mis, field16(54 + at));
               if (proto == 17) {
                 g_off[3] = 58, g_val[3] = nn;
-                g_fix_t += cv(nn) - cv(field16(58));
+                g_fix_t += cv(mis, nn) - cv(mis, field16(58));
                 g_nz = true;
               }
             }
@@ -278,125 +227,15 @@ ingress_verify_kernel(IngBytes<GEN>* __restrict__ bytes, const uint64_t* __restr
         const int32_t kk = (int32_t)((o + mis) >> 2) - kstart;
         return __builtin_amdgcn_alignbyte(rowword(kk + 1), rowword(kk), (o + mis) & 3u);
       };
-      if (L < 14) {
-        v = kErrTruncatedFrame;
-      } else {
-        const uint32_t et = be(H0, 0);
-        bool eth_drop = false, et_handler = true;
-        if (FILT && filt.on) {
-          // StackEthernet.Demux (internet/stack-ethernet.go:146-152), before
-          // ValidateSize: a frame neither broadcast nor for the stack's MAC is
-          // dropped unless multicast frames are accepted and the group bit is set
-          const uint32_t* w = base + (mis >> 2);
-          const uint32_t sm = mis & 3u, m0 = w[0], m1 = w[1], m2 = w[2];
-          const uint32_t D0 = __builtin_amdgcn_alignbyte(m1, m0, sm), D1 = __builtin_amdgcn_alignbyte(m2, m1, sm) & 0xFFFFu;
-          const bool bcast = D0 == 0xFFFFFFFFu && D1 == 0xFFFFu;
-          const bool mine = D0 == filt.mac_lo && D1 == filt.mac_hi;
-          eth_drop = !bcast && !mine && !(filt.eth_mc && (D0 & 1u));
-          // handlers.demuxByProto(etype) (stack-ethernet.go:158-161): no handler -> drop
-          et_handler = false;
-#pragma unroll
-          for (int i = 0; i < 8; ++i) et_handler = et_handler || (i < (int)filt.n_et && filt.et[i] == et);
-        }
-        if (eth_drop) {
-          v = kErrPacketDrop;
-        } else if (et <= 1500 && L < et) {
-          v = kErrInvalidLengthField;
-        } else if (et == 0x8100 && L < 18) {
-          v = kErrTruncatedFrame;
-        } else if (!et_handler) {
-          v = kErrPacketDrop;
-        } else if (et == 0x0800) {
-          const uint32_t M = L - 14;
-          if (M < 20) {
-            v = kErrTruncatedFrame;
-          } else {
-            const uint32_t b0 = byt(H0, 2), tl = be(H1, 0), ihl = b0 & 15u;
-            if (FILT && filt.on && filt.ip4 != 0u) {
-              // demux4's destination check (internet/stack-ip4.go:108-119), before ValidateExceptCRC
-              const uint32_t dst = field32(30);
-              const bool mc = (dst & 0xF0u) == 0xE0u, bc = dst == 0xFFFFFFFFu;  // ipv4/definitions.go:17-36
-              if (dst != filt.ip4 && !(filt.ip4_mc && mc) && !(filt.ip4_bc && bc)) v = kErrPacketDrop;
-            }
-            if (v != 0) {
-            } else if (tl < 20) v = kErrInvalidLengthField;
-            else if (tl > M) v = kErrTruncatedFrame;
-            else if (ihl < 5 || ihl * 4 > tl) v = kErrInvalidLengthField;
-            else if ((b0 >> 4) != 4) v = kErrInvalidField;
-            else if ((flags & kVerifyEvilBit) && (be(H2, 0) & (1u << 13))) v = kErrPacketDrop;
-            if (v == 0) {
-              hdr_sum = true;
-              const uint32_t hl = ihl * 4, proto = byt(H2, 3), P = tl - hl;
-              if (FILT && filt.on && !proto_bit(filt.p4, proto)) {
-                v_udp4 = kErrPacketDrop;  // nodeByProto nil (stack-ip4.go:135-141), after the header sum
-              } else if (proto == 6) {
-                l4_sum = true;
-                pa = 26, pb = 34, la = 14 + hl, lb = 14 + tl;
-                lseed = ((tl - hl) & 0xFFFFu) + 6u;
-              } else if (proto == 17) {
-                if (P < 8) {
-                  v_udp4 = kErrTruncatedFrame;
-                } else {
-                  const uint32_t ul = field16(14 + hl + 4);
-                  if (ul < 8) v_udp4 = kErrInvalidLengthField;
-                  else if (ul > P) v_udp4 = kErrTruncatedFrame;
-                  else {
-                    l4_sum = true;
-                    pa = 26, pb = 34, la = 14 + hl, lb = 14 + hl + ul;
-                    lseed = ul + 17u;
-                  }
-                }
-              } else if (proto == 1 && (flags & kVerifyIcmp)) {
-                if (P < 8) {
-                  v_udp4 = kErrTruncatedFrame;
-                } else {
-                  const uint32_t type = field16(14 + hl) >> 8;
-                  if (type != 0 && type != 8) {
-                    v_udp4 = kErrPacketDrop;
-                  } else {
-                    l4_sum = true;  // no pseudo-header: [pa, pb) empty, lseed 0
-                    la = 14 + hl, lb = 14 + tl;
-                  }
-                }
-              }
-            }
-          }
-        } else if (et == 0x86DD) {
-          const uint32_t M = L - 14;
-          if (M < 40) {
-            v = kErrTruncatedFrame;
-          } else {
-            const uint32_t pl = be(H1, 2), proto = byt(H2, 0);
-            if (FILT && filt.on && (filt.ip6[0] | filt.ip6[1] | filt.ip6[2] | filt.ip6[3]) != 0u) {
-              // demux6's destination check (internet/stack-ip6.go:93-98), before ValidateSize
-              const uint32_t d0 = field32(38), d1 = field32(42), d2 = field32(46), d3 = field32(50);
-              const bool mine = d0 == filt.ip6[0] && d1 == filt.ip6[1] && d2 == filt.ip6[2] && d3 == filt.ip6[3];
-              if (!mine && !(filt.ip6_mc && (d0 & 0xFFu) == 0xFFu)) v = kErrPacketDrop;  // internal/ip.go:30-35
-            }
-            if (v != 0) {
-            } else if (pl + 40 > M) {
-              v = kErrInvalidLengthField;
-            } else if (FILT && filt.on && !proto_bit(filt.p6, proto)) {
-              v = kErrPacketDrop;  // nodeByProto nil (stack-ip6.go:107-111), before the sums
-            } else if (proto == 6 || proto == 17 || (proto == 58 && (flags & kVerifyIcmp))) {
-              // demux6 size-checks the UDP header only; TCP goes straight to the
-              // sum (internet/stack-ip6.go:116-137), whatever pl is.  ICMPv6:
-              // icmpv6.NewFrame's size check, then the same pseudo-header sum.
-              if (proto == 58 && pl < 8) v = kErrTruncatedFrame;
-              if (proto == 17) {
-                if (pl < 8) v = kErrTruncatedFrame;
-                else if (field16(58) < 8) v = kErrInvalidLengthField;
-                else if (field16(58) > pl) v = kErrTruncatedFrame;
-              }
-              if (v == 0) {
-                l4_sum = true;
-                pa = 22, pb = 54, la = 54, lb = 54 + pl;  // AddUint32(pl), AddUint32(proto): high halves 0
-                lseed = pl + proto;
-              }
-            }
-          }
-        }
-      }
+      // destination MAC: the frame's first dwords, below the row's window
+      auto mac = [&](uint32_t& D0, uint32_t& D1) {
+        const uint32_t* w = base + (mis >> 2);
+        const uint32_t sm = mis & 3u, m0 = w[0], m1 = w[1], m2 = w[2];
+        D0 = __builtin_amdgcn_alignbyte(m1, m0, sm), D1 = __builtin_amdgcn_alignbyte(m2, m1, sm) & 0xFFFFu;
+      };
+      rx = rx_plan<FILT>(L, flags, filt, be16, byte_at, field32, field16, mac);
+      v = rx.v, hdr_sum = rx.hdr_sum, l4_sum = rx.l4_sum;
+      pa = rx.pa, pb = rx.pb, la = rx.la, lb = rx.lb, lseed = rx.lseed;
     }
 
     // ---- the sums: the first batch is in x; later batches while the summed
@@ -404,18 +243,9 @@ ingress_verify_kernel(IngBytes<GEN>* __restrict__ bytes, const uint64_t* __restr
     uint32_t hE = 0, hO = 0, tE = 0, tO = 0;
     // qword rows: S = the sum of the little-endian 16-bit halves of the
     // aligned dwords, one v_dot2_u32_u16 per dword (the dword rows keep the
-    // even / odd byte sums E, O of two v_dot4 per dword).  S = Σ bytes at even
-    // addresses + 256 Σ bytes at odd addresses; with the frame starting at an
-    // odd address that is 256 E + O itself, at an even one E + 256 O, which is
-    // 256 E + O times 256 modulo 65535 (a byte rotation of the folded sum).
-    // The sums of a frame under 64 KiB never wrap 2^32, so sum16 of the
-    // rotated fold equals sum16 of 256 E + O (RFC 1071 §2(B)).
+    // even / odd byte sums E, O of two v_dot4 per dword); conv (frame_plan.hpp)
+    // turns S into 256 E + O
     uint32_t hS = 0, tS = 0;
-    auto dot2 = [](uint32_t w, uint32_t acc) -> uint32_t {
-      typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
-      const u16x2 ones = {1, 1};
-      return __builtin_amdgcn_udot2(__builtin_bit_cast(u16x2, w), ones, acc, false);
-    };
     const bool any_sum = hdr_sum || l4_sum;
     const int32_t end = l4_sum ? lb : (hdr_sum ? 34 : 0);
     const int32_t kend = any_sum ? (end + (int32_t)mis + 3) >> 2 : 0;
@@ -491,7 +321,7 @@ ingress_verify_kernel(IngBytes<GEN>* __restrict__ bytes, const uint64_t* __restr
       }
       // bytes at or past lb of the last qword (zero unless this lane kept it)
       const int32_t ol = 8 * (qend - 1) - (int32_t)mis;  // frame offset of its first byte
-      const uint32_t j0 = yl.x & ing_keep_from(lb - ol), j1 = yl.y & ing_keep_from(lb - ol - 4);
+      const uint32_t j0 = yl.x & keep_from(lb - ol), j1 = yl.y & keep_from(lb - ol - 4);
       tS -= dot2(j0, dot2(j1, 0u));
     }
     for (int32_t k0 = kstart + (int32_t)p; !QW && k0 < kend; k0 += 16 * UNR) {
@@ -518,21 +348,15 @@ ingress_verify_kernel(IngBytes<GEN>* __restrict__ bytes, const uint64_t* __restr
     uint32_t hX, tX;
     if constexpr (QW) {
       // GEN: the field fixes are row-uniform, added on lane 0 of the row only
-      hS = row_add(hS + (p == 0 ? g_fix_h : 0u)), tS = row_add(tS + (p == 0 ? g_fix_t : 0u));
-      auto conv = [&](uint32_t S) -> uint32_t {
-        if (mis & 1u) return S;
-        uint32_t f = (S & 0xFFFFu) + (S >> 16);
-        f = (f & 0xFFFFu) + (f >> 16);
-        return ((f << 8) | (f >> 8)) & 0xFFFFu;
-      };
-      hX = conv(hS), tX = conv(tS);
+      hS = row_add16(hS + (p == 0 ? g_fix_h : 0u)), tS = row_add16(tS + (p == 0 ? g_fix_t : 0u));
+      hX = conv(mis, hS), tX = conv(mis, tS);
     } else {
-      hE = row_add(hE), hO = row_add(hO), tE = row_add(tE), tO = row_add(tO);
+      hE = row_add16(hE), hO = row_add16(hO), tE = row_add16(tE), tO = row_add16(tO);
       hX = 256u * hE + hO, tX = 256u * tE + tO;
     }
     if constexpr (GEN) {
-      g_val[1] = ing_sum16(hX);
-      const uint32_t tc = ing_sum16(tX + lseed);
+      g_val[1] = fold_sum16(hX);
+      const uint32_t tc = fold_sum16(tX + lseed);
       g_val[2] = g_nz && tc == 0 ? 0xFFFFu : tc;
       // lane k < 4 stores field k (big-endian): one 16-bit store when the
       // field's address is even, else its two bytes
@@ -549,9 +373,7 @@ ingress_verify_kernel(IngBytes<GEN>* __restrict__ bytes, const uint64_t* __restr
         }
       }
     } else {
-      if (v == 0 && hdr_sum && ing_sum16(hX) != 0) v = kErrBadCRC;
-      if (v == 0) v = v_udp4;  // udp.NewFrame / ValidateSize follow CalculateHeaderCRC (stack-ip4.go:128-159)
-      if (v == 0 && l4_sum && ing_sum16(tX + lseed) != 0) v = kErrBadCRC;
+      v = rx_verdict(rx, hX, tX);
     }
     if (live && p == 0) verdict[f] = (uint8_t)v;
   }

@@ -32,25 +32,12 @@
 // the loads never fault.
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include "wave_util.hpp"
 
 namespace lnx {
 
 constexpr int kPcapBlock = 256;
 constexpr uint32_t kPcapErrInvalidLengthField = 15, kPcapErrTruncatedFrame = 18;
-
-__device__ __forceinline__ uint32_t pcap_keep_from(int32_t lo) {
-  lo = lo < 0 ? 0 : (lo > 4 ? 4 : lo);
-  return (uint32_t)(0xFFFFFFFFull << (8 * lo));
-}
-// byte mask of the frame offsets [a, b) inside the dword whose byte 0 is at o
-__device__ __forceinline__ uint32_t pcap_range(int32_t o, int32_t a, int32_t b) {
-  return pcap_keep_from(a - o) & ~pcap_keep_from(b - o);
-}
-
-__device__ __forceinline__ uint32_t pcap_fold(uint32_t sum) {  // crc.go:17-21
-  sum = (sum & 0xffffu) + (sum >> 16);
-  return (uint16_t)~(uint16_t)(sum + (sum >> 16));
-}
 
 // the sums' contributions of one 16-byte block at frame offset o
 __device__ __forceinline__ void pcap_block(const uint4& v, int32_t o, int32_t hA, int32_t hB, int32_t a1, int32_t b1,
@@ -60,8 +47,8 @@ __device__ __forceinline__ void pcap_block(const uint4& v, int32_t o, int32_t hA
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     const int32_t oj = o + 4 * j;
-    const uint32_t xh = w[j] & pcap_range(oj, hA, hB);
-    const uint32_t xt = w[j] & (pcap_range(oj, a1, b1) | pcap_range(oj, a2, b2));
+    const uint32_t xh = w[j] & range_mask(oj, hA, hB);
+    const uint32_t xt = w[j] & (range_mask(oj, a1, b1) | range_mask(oj, a2, b2));
     hE = __builtin_amdgcn_udot4(xh, 0x00010001u, hE, false);
     hO = __builtin_amdgcn_udot4(xh, 0x01000100u, hO, false);
     tE = __builtin_amdgcn_udot4(xt, 0x00010001u, tE, false);
@@ -178,8 +165,8 @@ pcap_rows_kernel(const uint8_t* __restrict__ bytes, const uint64_t* __restrict__
       ts += (uint32_t)__shfl_xor((int)ts, sft, 16);
     }
     uint32_t st = code << 2;
-    if (sum_h && pcap_fold(hs) != 0) st |= 1u;
-    if (sum_t && pcap_fold(ts + seed) != 0) st |= 2u;
+    if (sum_h && fold_sum16(hs) != 0) st |= 1u;
+    if (sum_t && fold_sum16(ts + seed) != 0) st |= 2u;
     if (valid && rl == 0) status[f] = (uint8_t)st;
   }
 }

@@ -23,7 +23,9 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <type_traits>
+#include "frame_plan.hpp"
 #include "rx_filter.hpp"
+#include "wave_util.hpp"
 
 namespace lnx {
 
@@ -49,9 +51,6 @@ constexpr int kTxBlock = LNX_TX_BLOCK;
 #endif
 constexpr int kTxBlockHost = LNX_TX_BLOCK_HOST;
 constexpr int kRvUnroll = 12;  // qwords per lane per batch (1536 bytes per row, as the ingress kernel)
-constexpr uint32_t kErrPacketDrop = 2, kErrBadCRC = 3, kErrInvalidField = 14, kErrInvalidLengthField = 15,
-                   kErrTruncatedFrame = 18;
-constexpr uint32_t kVerifyEvilBit = 1, kVerifyIcmp = 2;
 // LDS (bytes): the slicing tables T_k (k < 4: Z_{128}(e << 8k); 4 + k: Z_{124}(e << 8k)) expanded into
 // 8 bank columns (e << 8 | k << 5 | c << 2), then F_q = Z_{-8q} (q < 32) and B_b = Z_{-b} (b < 8) as
 // nibble tables, entry (t, i, v) at 128 t + 16 i + v dwords
@@ -122,44 +121,6 @@ __device__ __forceinline__ uint32_t rv_nib_f(const char* lds, uint32_t q, uint32
   }
   return a;
 }
-__device__ __forceinline__ uint32_t rv_row_xor(uint32_t v) {
-  v ^= (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xB1, 0xF, 0xF, false);   // quad_perm [1,0,3,2]
-  v ^= (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x4E, 0xF, 0xF, false);   // quad_perm [2,3,0,1]
-  v ^= (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x124, 0xF, 0xF, false);  // row_ror:4
-  v ^= (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x128, 0xF, 0xF, false);  // row_ror:8
-  return v;
-}
-__device__ __forceinline__ uint32_t rv_row_add(uint32_t v) {
-  v += (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xB1, 0xF, 0xF, false);
-  v += (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x4E, 0xF, 0xF, false);
-  v += (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x124, 0xF, 0xF, false);
-  v += (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x128, 0xF, 0xF, false);
-  return v;
-}
-__device__ __forceinline__ bool rv_proto_bit(const uint32_t (&m)[8], uint32_t proto) {
-  const uint32_t w = proto >> 5;
-  const uint32_t word = w == 0 ? m[0] : w == 1 ? m[1] : w == 2 ? m[2] : w == 3 ? m[3] : w == 4 ? m[4]
-                        : w == 5 ? m[5] : w == 6 ? m[6] : m[7];
-  return (word >> (proto & 31u)) & 1u;
-}
-__device__ __forceinline__ uint32_t rv_keep_from(int32_t lo) {
-  lo = lo < 0 ? 0 : (lo > 4 ? 4 : lo);
-  return (uint32_t)(0xFFFFFFFFull << (8 * lo));
-}
-// byte mask of the frame offsets [a, b) inside the word whose byte 0 is at o0
-__device__ __forceinline__ uint32_t rv_range(int32_t o0, int32_t a, int32_t b) {
-  return rv_keep_from(a - o0) & ~rv_keep_from(b - o0);
-}
-__device__ __forceinline__ uint16_t rv_sum16(uint32_t sum) {  // crc.go:17-21
-  sum = (sum & 0xffffu) + (sum >> 16);
-  return (uint16_t)~(uint16_t)(sum + (sum >> 16));
-}
-__device__ __forceinline__ uint32_t rv_dot2(uint32_t w, uint32_t acc) {
-  typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
-  const u16x2 ones = {1, 1};
-  return __builtin_amdgcn_udot2(__builtin_bit_cast(u16x2, w), ones, acc, false);
-}
-
 }  // namespace
 
 // frame f = bytes[off[f] : off[f+1]] (offsets mode) or bytes[off[f] :
@@ -225,20 +186,6 @@ __device__ __attribute__((aligned(16))) uint32_t g_rv_zero4[4];
 __device__ __forceinline__ rv_u4 rv_ld4(const rv_u4* p) {
   return *(const __attribute__((address_space(1))) rv_u4*)p;
 }
-// the XOR / sum over an 8-lane row (two quad steps, then the other quad of the half row)
-__device__ __forceinline__ uint32_t rv_row8_xor(uint32_t v) {
-  v ^= (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xB1, 0xF, 0xF, false);   // quad_perm [1,0,3,2]
-  v ^= (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x4E, 0xF, 0xF, false);   // quad_perm [2,3,0,1]
-  v ^= (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x141, 0xF, 0xF, false);  // row_half_mirror
-  return v;
-}
-__device__ __forceinline__ uint32_t rv_row8_add(uint32_t v) {
-  v += (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xB1, 0xF, 0xF, false);
-  v += (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x4E, 0xF, 0xF, false);
-  v += (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x141, 0xF, 0xF, false);
-  return v;
-}
-
 // Phase A for the group's short frames (round 6): positions [0, n8) of the
 // passes' order, every frame there at most 128 (kR8Lines - 1) bytes (its
 // window at most kR8Lines lines), in passes of EIGHT 8-lane rows.  Lane p of a
@@ -355,19 +302,19 @@ __device__ __forceinline__ void rv_rows8(const char* lds, uint2* res, uint2* hea
         const int32_t o = 8 * (2 * (int32_t)p + v + 16 * u) - (int32_t)m16;  // the qword's first frame offset
         const uint32_t c0 = y[u][2 * v], c1 = y[u][2 * v + 1];
         if (u == 0) {
-          S = rv_dot2(c0 & rv_range(o, 14, (int32_t)L), rv_dot2(c1 & rv_range(o + 4, 14, (int32_t)L), S));
+          S = dot2(c0 & range_mask(o, 14, (int32_t)L), dot2(c1 & range_mask(o + 4, 14, (int32_t)L), S));
         } else {
-          S = rv_dot2(c0 & ~rv_keep_from((int32_t)L - o), rv_dot2(c1 & ~rv_keep_from((int32_t)L - o - 4), S));
+          S = dot2(c0 & ~keep_from((int32_t)L - o), dot2(c1 & ~keep_from((int32_t)L - o - 4), S));
         }
         if constexpr (CRC) {
           const int32_t ie = (int32_t)(Lc < 4 ? Lc : 4u);
           uint32_t d0, d1;
           if (u == 0) {
-            d0 = (c0 & rv_range(o, 0, (int32_t)Lt)) ^ rv_range(o, 0, ie);
-            d1 = (c1 & rv_range(o + 4, 0, (int32_t)Lt)) ^ rv_range(o + 4, 0, ie);
+            d0 = (c0 & range_mask(o, 0, (int32_t)Lt)) ^ range_mask(o, 0, ie);
+            d1 = (c1 & range_mask(o + 4, 0, (int32_t)Lt)) ^ range_mask(o + 4, 0, ie);
           } else {
-            d0 = c0 & ~rv_keep_from((int32_t)Lt - o);
-            d1 = c1 & ~rv_keep_from((int32_t)Lt - o - 4);
+            d0 = c0 & ~keep_from((int32_t)Lt - o);
+            d1 = c1 & ~keep_from((int32_t)Lt - o - 4);
           }
           const uint32_t nr = rv_unit(lds, r[v] ^ d0, d1, z);
           r[v] = u < NL ? nr : r[v];
@@ -379,11 +326,11 @@ __device__ __forceinline__ void rv_rows8(const char* lds, uint2* res, uint2* hea
       // the window ends W = 128 NL - m16 past the frame start; W - Lc = 8a + b
       const uint32_t pad = (uint32_t)(128 * NL - (int32_t)m16 - (int32_t)Lc);
       const uint32_t a = pad >> 3, b = pad & 7u;
-      const uint32_t x = rv_row8_xor(rv_nib_f(lds, 2u * p + a, r[0]) ^ rv_nib_f(lds, 2u * p + 1u + a, r[1]));
+      const uint32_t x = row_xor8(rv_nib_f(lds, 2u * p + a, r[0]) ^ rv_nib_f(lds, 2u * p + 1u + a, r[1]));
       const uint32_t R = rv_nib(lds, kRvB + 512u * b, x);
       okf = TX ? R : (uint32_t)(Lt >= 4 && ~R == 0x2144DF1Cu);
     }
-    S = rv_row8_add(S);
+    S = row_add8(S);
     if (p == 0) res[k] = make_uint2(okf, S);
   }
 }
@@ -558,14 +505,14 @@ __device__ __forceinline__ uint32_t rv_rows(const char* lds, uint2* res, uint2* 
         if (u == 0 && it == 0) {
           // line 0: the sum from frame offset 14 on; the CRC over the frame's bytes, init on 0..3
           const int32_t o0 = 8 * (int32_t)p - (int32_t)mis;
-          S = rv_dot2(c0 & rv_keep_from(14 - o0), rv_dot2(c1 & rv_keep_from(10 - o0), S));
+          S = dot2(c0 & keep_from(14 - o0), dot2(c1 & keep_from(10 - o0), S));
           if constexpr (CRC) {
             const int32_t ie = (int32_t)(Lc < 4 ? Lc : 4u);
-            c0 = (c0 & rv_range(o0, 0, (int32_t)Lt)) ^ rv_range(o0, 0, ie);
-            c1 = (c1 & rv_range(o0 + 4, 0, (int32_t)Lt)) ^ rv_range(o0 + 4, 0, ie);
+            c0 = (c0 & range_mask(o0, 0, (int32_t)Lt)) ^ range_mask(o0, 0, ie);
+            c1 = (c1 & range_mask(o0 + 4, 0, (int32_t)Lt)) ^ range_mask(o0 + 4, 0, ie);
           }
         } else {
-          S = rv_dot2(c0, rv_dot2(c1, S));
+          S = dot2(c0, dot2(c1, S));
         }
         if constexpr (CRC) {
           const uint32_t nr = rv_unit(lds, r ^ c0, c1, z);
@@ -628,21 +575,21 @@ __device__ __forceinline__ uint32_t rv_rows(const char* lds, uint2* res, uint2* 
         if (!cap4) ye = rv_ld(qme >= 0 ? base2 + qme : zero);  // (an L2 hit: the fold just read it)
       }
       const int32_t oe = 8 * qme - (int32_t)mis;
-      S -= rv_dot2(ye.x & rv_keep_from((int32_t)L - oe), rv_dot2(ye.y & rv_keep_from((int32_t)L - oe - 4), 0u)) &
+      S -= dot2(ye.x & keep_from((int32_t)L - oe), dot2(ye.y & keep_from((int32_t)L - oe - 4), 0u)) &
            (qme >= 0 && L >= 14 ? ~0u : 0u);
       uint32_t okf = 1;
       if constexpr (CRC) {
         const bool junk = qme == lastq && lastq >= 16;
-        r ^= rv_unit(lds, junk ? ye.x & rv_keep_from((int32_t)Lt - oe) : 0u,
-                     junk ? ye.y & rv_keep_from((int32_t)Lt - oe - 4) : 0u, z);
+        r ^= rv_unit(lds, junk ? ye.x & keep_from((int32_t)Lt - oe) : 0u,
+                     junk ? ye.y & keep_from((int32_t)Lt - oe - 4) : 0u, z);
         // the window ends W = 128 NL - mis (frame offsets) past the frame start; W - Lc = 8a + b
         const uint32_t pad = (uint32_t)(128 * NL - (int32_t)mis - (int32_t)Lc);
         const uint32_t a = pad >> 3, b = pad & 7u;
-        const uint32_t x = rv_row_xor(rv_nib_f(lds, p + a, r));
+        const uint32_t x = row_xor16(rv_nib_f(lds, p + a, r));
         const uint32_t R = rv_nib(lds, kRvB + 512u * b, x);
         okf = TX ? R : (uint32_t)(Lt >= 4 && ~R == 0x2144DF1Cu);
       }
-      S = rv_row_add(S);
+      S = row_add16(S);
       if (p == 0) res[k] = make_uint2(okf, S);
     }
     return rank;
@@ -767,7 +714,7 @@ rx_verify_kernel(const uint8_t* __restrict__ bytes, const uint64_t* __restrict__
       uint32_t acc = 0;
 #pragma unroll
       for (int d = decltype(D0)::value; d < decltype(D1)::value; ++d)
-        acc = rv_dot2(dw[d] & rv_range(4 * d - (int32_t)mis, a, b), acc);
+        acc = dot2(dw[d] & range_mask(4 * d - (int32_t)mis, a, b), acc);
       return acc;
     };
     using I3 = std::integral_constant<int, 3>;
@@ -778,120 +725,12 @@ rx_verify_kernel(const uint8_t* __restrict__ bytes, const uint64_t* __restrict__
     using I18 = std::integral_constant<int, 18>;
     using I22 = std::integral_constant<int, 22>;
 
-    // ---- header parse (ingress_kernel.hip's, FCS excluded: L bytes)
-    uint32_t v = 0, v_udp4 = 0;
-    bool hdr_sum = false, l4_sum = false;
-    int32_t pa = 0, pb = 0, la = 0, lb = 0;
-    uint32_t lseed = 0;
-    if (L < 14) {
-      v = kErrTruncatedFrame;
-    } else {
-      const uint32_t et = be16(12);
-      bool eth_drop = false, et_handler = true;
-      if (FILT && filt.on) {
-        // StackEthernet.Demux (internet/stack-ethernet.go:146-152), before ValidateSize
-        const uint32_t D0 = F[0], D1 = F[1] & 0xFFFFu;
-        const bool bcast = D0 == 0xFFFFFFFFu && D1 == 0xFFFFu;
-        const bool mine = D0 == filt.mac_lo && D1 == filt.mac_hi;
-        eth_drop = !bcast && !mine && !(filt.eth_mc && (D0 & 1u));
-        et_handler = false;  // handlers.demuxByProto(etype) (stack-ethernet.go:158-161)
-#pragma unroll
-        for (int i = 0; i < 8; ++i) et_handler = et_handler || (i < (int)filt.n_et && filt.et[i] == et);
-      }
-      if (eth_drop) {
-        v = kErrPacketDrop;
-      } else if (et <= 1500 && L < et) {
-        v = kErrInvalidLengthField;
-      } else if (et == 0x8100 && L < 18) {
-        v = kErrTruncatedFrame;
-      } else if (!et_handler) {
-        v = kErrPacketDrop;
-      } else if (et == 0x0800) {
-        const uint32_t M = L - 14;
-        if (M < 20) {
-          v = kErrTruncatedFrame;
-        } else {
-          const uint32_t b0 = byt(F[3], 2), tl = be16(16), ihl = b0 & 15u;
-          if (FILT && filt.on && filt.ip4 != 0u) {
-            const uint32_t dst = le32(30);  // demux4's destination check (stack-ip4.go:108-119)
-            const bool mc = (dst & 0xF0u) == 0xE0u, bc = dst == 0xFFFFFFFFu;
-            if (dst != filt.ip4 && !(filt.ip4_mc && mc) && !(filt.ip4_bc && bc)) v = kErrPacketDrop;
-          }
-          if (v != 0) {
-          } else if (tl < 20) v = kErrInvalidLengthField;
-          else if (tl > M) v = kErrTruncatedFrame;
-          else if (ihl < 5 || ihl * 4 > tl) v = kErrInvalidLengthField;
-          else if ((b0 >> 4) != 4) v = kErrInvalidField;
-          else if ((flags & kVerifyEvilBit) && (be16(20) & (1u << 13))) v = kErrPacketDrop;
-          if (v == 0) {
-            hdr_sum = true;
-            const uint32_t hl = ihl * 4, proto = byt(F[5], 3), P = tl - hl;
-            if (FILT && filt.on && !rv_proto_bit(filt.p4, proto)) {
-              v_udp4 = kErrPacketDrop;  // nodeByProto nil (stack-ip4.go:135-141), after the header sum
-            } else if (proto == 6) {
-              l4_sum = true;
-              pa = 26, pb = 34, la = 14 + hl, lb = 14 + tl;
-              lseed = ((tl - hl) & 0xFFFFu) + 6u;
-            } else if (proto == 17) {
-              if (P < 8) {
-                v_udp4 = kErrTruncatedFrame;
-              } else {
-                const uint32_t ul = dyn16(14 + hl + 4);
-                if (ul < 8) v_udp4 = kErrInvalidLengthField;
-                else if (ul > P) v_udp4 = kErrTruncatedFrame;
-                else {
-                  l4_sum = true;
-                  pa = 26, pb = 34, la = 14 + hl, lb = 14 + hl + ul;
-                  lseed = ul + 17u;
-                }
-              }
-            } else if (proto == 1 && (flags & kVerifyIcmp)) {
-              if (P < 8) {
-                v_udp4 = kErrTruncatedFrame;
-              } else {
-                const uint32_t type = dyn16(14 + hl) >> 8;
-                if (type != 0 && type != 8) {
-                  v_udp4 = kErrPacketDrop;
-                } else {
-                  l4_sum = true;
-                  la = 14 + hl, lb = 14 + tl;
-                }
-              }
-            }
-          }
-        }
-      } else if (et == 0x86DD) {
-        const uint32_t M = L - 14;
-        if (M < 40) {
-          v = kErrTruncatedFrame;
-        } else {
-          const uint32_t pl = be16(18), proto = byt(F[5], 0);
-          if (FILT && filt.on && (filt.ip6[0] | filt.ip6[1] | filt.ip6[2] | filt.ip6[3]) != 0u) {
-            const uint32_t d0 = le32(38), d1 = le32(42), d2 = le32(46), d3 = le32(50);
-            const bool mine = d0 == filt.ip6[0] && d1 == filt.ip6[1] && d2 == filt.ip6[2] && d3 == filt.ip6[3];
-            if (!mine && !(filt.ip6_mc && (d0 & 0xFFu) == 0xFFu)) v = kErrPacketDrop;
-          }
-          if (v != 0) {
-          } else if (pl + 40 > M) {
-            v = kErrInvalidLengthField;
-          } else if (FILT && filt.on && !rv_proto_bit(filt.p6, proto)) {
-            v = kErrPacketDrop;
-          } else if (proto == 6 || proto == 17 || (proto == 58 && (flags & kVerifyIcmp))) {
-            if (proto == 58 && pl < 8) v = kErrTruncatedFrame;
-            if (proto == 17) {
-              if (pl < 8) v = kErrTruncatedFrame;
-              else if (be16(58) < 8) v = kErrInvalidLengthField;
-              else if (be16(58) > pl) v = kErrTruncatedFrame;
-            }
-            if (v == 0) {
-              l4_sum = true;
-              pa = 22, pb = 54, la = 54, lb = 54 + pl;
-              lseed = pl + proto;
-            }
-          }
-        }
-      }
-    }
+    // ---- header parse (frame_plan.hpp; FCS excluded: L bytes)
+    auto mac = [&](uint32_t& D0, uint32_t& D1) { D0 = F[0], D1 = F[1] & 0xFFFFu; };
+    auto byte_at = [&](int o) -> uint32_t { return byt(F[o >> 2], o & 3); };
+    const RxPlan rx = rx_plan<FILT>(L, flags, filt, be16, byte_at, le32, dyn16, mac);
+    const bool hdr_sum = rx.hdr_sum, l4_sum = rx.l4_sum;
+    const int32_t pa = rx.pa, pb = rx.pb, la = rx.la, lb = rx.lb;
 
     // ---- the sums: header [14, 34) and pseudo-header [pa, pb) from the staged
     // bytes; the segment [la, lb) = S - [14, la) - [lb, L)
@@ -926,7 +765,7 @@ rx_verify_kernel(const uint8_t* __restrict__ bytes, const uint64_t* __restrict__
         const int32_t q = qb + (int32_t)lane;
         const uint2 t = rv_ld(q < q1 ? kb + q : zero);
         const int32_t o0 = 8 * q - (int32_t)m2;
-        acc = rv_dot2(t.x & rv_range(o0, a, b), rv_dot2(t.y & rv_range(o0 + 4, a, b), acc));
+        acc = dot2(t.x & range_mask(o0, a, b), dot2(t.y & range_mask(o0 + 4, a, b), acc));
       }
 #pragma unroll
       for (int sft = 1; sft < 64; sft <<= 1) acc += (uint32_t)__shfl_xor((int)acc, sft);
@@ -935,16 +774,7 @@ rx_verify_kernel(const uint8_t* __restrict__ bytes, const uint64_t* __restrict__
     const uint2 rk = res[kk];
     // [14, la): la <= 74; [pa, pb) within [22, 54)
     if (l4_sum) tS = rk.y - hsum(I3{}, I22{}, 14, la) - tS + hsum(I5{}, I16{}, pa, pb);
-    auto conv = [&](uint32_t S) -> uint32_t {  // ingress_kernel.hip: the byte rotation for even bases
-      if (mis & 1u) return S;
-      uint32_t fo = (S & 0xFFFFu) + (S >> 16);
-      fo = (fo & 0xFFFFu) + (fo >> 16);
-      return ((fo << 8) | (fo >> 8)) & 0xFFFFu;
-    };
-    const uint32_t hX = conv(hS), tX = conv(tS);
-    if (v == 0 && hdr_sum && rv_sum16(hX) != 0) v = kErrBadCRC;
-    if (v == 0) v = v_udp4;  // udp.NewFrame / ValidateSize follow CalculateHeaderCRC (stack-ip4.go:128-159)
-    if (v == 0 && l4_sum && rv_sum16(tX + lseed) != 0) v = kErrBadCRC;
+    const uint32_t v = rx_verdict(rx, conv(mis, hS), conv(mis, tS));
     if (live) {
       if (okv) okv[f] = (uint8_t)rk.x;  // (null: the verdicts alone, for lnx_ingress_verify_batch)
       verdict[f] = (uint8_t)v;
@@ -1116,7 +946,7 @@ tx_finish_kernel(uint8_t* __restrict__ bytes, const uint64_t* __restrict__ start
       uint32_t acc = 0;
 #pragma unroll
       for (int d = decltype(D0)::value; d < decltype(D1)::value; ++d)
-        acc = rv_dot2(dwd(d) & rv_range(4 * d - (int32_t)mis, a, b), acc);
+        acc = dot2(dwd(d) & range_mask(4 * d - (int32_t)mis, a, b), acc);
       return acc;
     };
     using I3 = std::integral_constant<int, 3>;
@@ -1124,10 +954,12 @@ tx_finish_kernel(uint8_t* __restrict__ bytes, const uint64_t* __restrict__ start
     using I11 = std::integral_constant<int, 11>;
     using I16 = std::integral_constant<int, 16>;
     using I22 = std::integral_constant<int, 22>;
-    // a 16-bit big-endian value at an even frame offset, as it adds to the LE half-word sums
-    auto cv = [&](uint32_t v) -> uint32_t { return (mis & 1u) ? v : (((v & 0xFFu) << 8) | (v >> 8)); };
-
-    // ---- the checksum step (ingress_kernel.hip GEN, oracle.tx_checksum)
+    // ---- the checksum step (oracle.tx_checksum): the generate rows' tree
+    // (ingress_kernel.hip GEN) restated.  Both stay inline: behind one shared
+    // function (the receive trees' form, frame_plan.hpp) each instance grew by
+    // 40-60 instructions and the Zipf mix ran slower, 1.6770 against 1.6644 ms
+    // for lnx_tx_checksum_batch and 2.9337 against 2.9256 ms for this kernel
+    // with the FCS (profiles/r12_frame_plan_ab.txt)
     uint32_t v = 0;
     uint32_t g_off[4] = {0, 0, 0, 0}, g_new[4] = {0, 0, 0, 0}, g_old[4] = {0, 0, 0, 0};
     bool hdr_sum = false, l4_sum = false, g_nz = false;
@@ -1152,17 +984,17 @@ tx_finish_kernel(uint8_t* __restrict__ bytes, const uint64_t* __restrict__ start
               hdr_sum = true;
               g_off[0] = 16, g_new[0] = tl, g_old[0] = be16(16);  // SetTotalLength(n + hl)
               g_off[1] = 24, g_old[1] = be16(24);                 // SetCRC(CalculateHeaderCRC())
-              g_fix_h = cv(tl) - cv(g_old[0]) - cv(g_old[1]);
+              g_fix_h = cv(mis, tl) - cv(mis, g_old[0]) - cv(mis, g_old[1]);
               if (need) {
                 l4_sum = true;
                 la = 14 + hl;
                 const uint32_t at = proto == 6 ? 16u : proto == 17 ? 6u : 2u;
                 g_off[2] = la + at, g_old[2] = dyn16(la + at);
-                g_fix_t = 0u - cv(g_old[2]);
+                g_fix_t = 0u - cv(mis, g_old[2]);
                 if (proto != 1) pa = 26, pb = 34, lseed = nn + proto;  // CRCWriteTCPPseudo / CRCWriteUDPPseudo(n)
                 if (proto == 17) {
                   g_off[3] = la + 4, g_new[3] = nn, g_old[3] = dyn16(la + 4);  // SetLength(n)
-                  g_fix_t += cv(nn) - cv(g_old[3]);
+                  g_fix_t += cv(mis, nn) - cv(mis, g_old[3]);
                   g_nz = true;
                 }
               }
@@ -1182,10 +1014,10 @@ tx_finish_kernel(uint8_t* __restrict__ bytes, const uint64_t* __restrict__ start
               lseed = nn + proto;
               const uint32_t at = proto == 6 ? 16u : proto == 17 ? 6u : 2u;
               g_off[2] = 54 + at, g_old[2] = dyn16(54 + at);
-              g_fix_t = 0u - cv(g_old[2]);
+              g_fix_t = 0u - cv(mis, g_old[2]);
               if (proto == 17) {
                 g_off[3] = 58, g_new[3] = nn, g_old[3] = be16(58);
-                g_fix_t += cv(nn) - cv(g_old[3]);
+                g_fix_t += cv(mis, nn) - cv(mis, g_old[3]);
                 g_nz = true;
               }
             }
@@ -1202,16 +1034,10 @@ tx_finish_kernel(uint8_t* __restrict__ bytes, const uint64_t* __restrict__ start
         dx[2 * i + 1] = v2.y;
       }
       const uint2 rk = res[kk];
-      auto conv = [&](uint32_t S) -> uint32_t {
-        if (mis & 1u) return S;
-        uint32_t fo = (S & 0xFFFFu) + (S >> 16);
-        fo = (fo & 0xFFFFu) + (fo >> 16);
-        return ((fo << 8) | (fo >> 8)) & 0xFFFFu;
-      };
-      if (hdr_sum) g_new[1] = rv_sum16(conv(hsum(I3{}, I11{}, 14, 34) + g_fix_h)) & 0xFFFFu;
+      if (hdr_sum) g_new[1] = fold_sum16(conv(mis, hsum(I3{}, I11{}, 14, 34) + g_fix_h)) & 0xFFFFu;
       if (l4_sum) {
         const uint32_t tS = rk.y - hsum(I3{}, I22{}, 14, la) + hsum(I5{}, I16{}, pa, pb) + g_fix_t;
-        const uint32_t tc = rv_sum16(conv(tS) + lseed) & 0xFFFFu;
+        const uint32_t tc = fold_sum16(conv(mis, tS) + lseed) & 0xFFFFu;
         g_new[2] = g_nz && tc == 0 ? 0xFFFFu : tc;
       }
     }

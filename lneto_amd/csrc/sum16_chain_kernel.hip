@@ -14,48 +14,22 @@
 //
 // The kernels live in namespace lnxs: the product library's lnx:: kernel list
 // is pinned by tests/test_abi.py, this namespace's by tests/test_sum_chain.py.
-// sum16_kernel.hip (lnx_sum16_batch's kernel) is untouched; the row helpers it
-// keeps to itself are restated here.
+// The row helpers shared with sum16_kernel.hip are wave_util.hpp's.
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include "wave_util.hpp"
 
 namespace lnxs {
+
+using lnx::fold_sum16;
+using lnx::keep8;
+using lnx::row_add16;
+using lnx::uniform64;
+using lnx::wave_add;
 
 constexpr int kBlock = 256;
 constexpr int kWaves = kBlock / 64;
 constexpr int kLineUnroll = 13;  // lines per row in flight (sum16_kernel.hip kLineUnroll)
-
-__device__ __forceinline__ uint16_t fold_sum16(uint32_t sum) {  // sum16, crc.go:17-21
-  sum = (sum & 0xffffu) + (sum >> 16);
-  return (uint16_t)~(uint16_t)(sum + (sum >> 16));
-}
-
-// Sum over each 16-lane row, the result in every lane of the row.
-__device__ __forceinline__ uint32_t row_add16(uint32_t v) {
-  v += (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xB1, 0xF, 0xF, false);   // quad_perm [1,0,3,2]
-  v += (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x4E, 0xF, 0xF, false);   // quad_perm [2,3,0,1]
-  v += (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x124, 0xF, 0xF, false);  // row_ror:4
-  v += (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x128, 0xF, 0xF, false);  // row_ror:8
-  return v;
-}
-// The four rows' sums joined in scalar registers (wave-uniform).
-__device__ __forceinline__ uint32_t wave_add(uint32_t v) {
-  v = row_add16(v);
-  return (uint32_t)__builtin_amdgcn_readlane((int)v, 0) + (uint32_t)__builtin_amdgcn_readlane((int)v, 16) +
-         (uint32_t)__builtin_amdgcn_readlane((int)v, 32) + (uint32_t)__builtin_amdgcn_readlane((int)v, 48);
-}
-
-__device__ __forceinline__ uint64_t keep8(int32_t d) {  // bytes [d, 8) of a qword, d clamped to 0..8
-  const uint32_t q = 4u * (uint32_t)(d < 0 ? 0 : (d > 8 ? 8 : d));
-  return (~0ull << q) << q;
-}
-
-// A value every lane holds alike, moved to scalar registers so that the
-// branches and loop bounds taken from it are scalar too.
-__device__ __forceinline__ uint64_t uniform64(uint64_t v) {
-  return (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v) |
-         ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32)) << 32);
-}
 
 enum class ByteMode : int { kPlanes = 0, kPartial = 1 };
 

@@ -17,32 +17,15 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <cstdlib>
+#include "wave_util.hpp"
 
 namespace lnx {
 
 constexpr int kSumBlock = 256;
 constexpr int kSumWaves = kSumBlock / 64;
 
-__device__ __forceinline__ uint16_t fold_sum16(uint32_t sum) {
-  sum = (sum & 0xffffu) + (sum >> 16);
-  return (uint16_t)~(uint16_t)(sum + (sum >> 16));
-}
-
 [[maybe_unused]] constexpr int kSumRowLanes = 16;  // one segment per 16-lane row, four per wave
 [[maybe_unused]] constexpr int kSumUnroll = 8;     // dwords per lane in flight per batch (512 B per row)
-
-__device__ __forceinline__ uint32_t sum_keep_from(int32_t lo) {
-  lo = lo < 0 ? 0 : (lo > 4 ? 4 : lo);
-  return (uint32_t)(0xFFFFFFFFull << (8 * lo));
-}
-
-__device__ __forceinline__ uint32_t row_add16(uint32_t v) {
-  v += (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xB1, 0xF, 0xF, false);   // quad_perm [1,0,3,2]
-  v += (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x4E, 0xF, 0xF, false);   // quad_perm [2,3,0,1]
-  v += (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x124, 0xF, 0xF, false);  // row_ror:4
-  v += (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x128, 0xF, 0xF, false);  // row_ror:8
-  return v;
-}
 
 // One 16-lane row per segment: lane p reads aligned dwords p, p+16, ... of the
 // segment's aligned span, kSumUnroll at a time, masks the bytes outside the
@@ -78,7 +61,7 @@ sum16_segments_kernel(const uint8_t* __restrict__ bytes, const uint64_t* __restr
 #pragma unroll
       for (int u = 0; u < kSumUnroll; ++u) {
         const int32_t o0 = (int32_t)(4 * (k0 + u * kSumRowLanes)) - (int32_t)mis;  // segment offset of byte 0
-        const uint32_t y = x[u] & sum_keep_from(-o0) & ~sum_keep_from((int32_t)L - o0);
+        const uint32_t y = x[u] & keep_from(-o0) & ~keep_from((int32_t)L - o0);
         E = __builtin_amdgcn_udot4(y, wE, E, false);
         O = __builtin_amdgcn_udot4(y, wO, O, false);
       }
@@ -98,11 +81,6 @@ sum16_segments_kernel(const uint8_t* __restrict__ bytes, const uint64_t* __restr
 // lines per row in flight: 13 covers a 1500-B segment in one round trip
 // (6.24 TB/s against 6.07 with 8 and 6.19 with 16, tools/prof/sum16_variants.py).
 constexpr int kLineUnroll = 13;
-
-__device__ __forceinline__ uint64_t keep8(int32_t d) {  // bytes [d, 8) of a qword, d clamped to 0..8
-  const uint32_t q = 4u * (uint32_t)(d < 0 ? 0 : (d > 8 ? 8 : d));
-  return (~0ull << q) << q;
-}
 
 // EDGE (with NT): the first line of each batch and its last two (where a
 // 12- or 13-line segment ends) are loaded with the default cache policy, the
