@@ -751,3 +751,158 @@ def ip4_option_frames(seed: int = 4015) -> list[tuple[str, bytes]]:
             b[14] = 0x40 | low
             out.append((f"tx/{l4}/ihl{low}/rand/40/ihl_low", bytes(b)))
     return out
+
+
+# ------------------------------------------------ near-miss destinations and every protocol value
+EDGE_IP4S = {"only_low": bytes([0, 0, 0, 1]), "only_high": bytes([1, 0, 0, 0])}   # stack addresses with one non-zero byte
+EDGE_IP6S = {"byte5": bytes(5) + b"\x01" + bytes(10), "byte10": bytes(10) + b"\x80" + bytes(5),
+             "byte15": bytes(15) + b"\x01"}
+EDGE_ETHERTYPES = (0x0000, 0x0001, 1500, 1501, 0x0800, 0x0806, 0x86DD, 0x8100, 0x88CC, 0x88A8, 0xFFFF) \
+    + tuple(0x0F0F * i for i in range(1, 17))   # sixteen spread values between 0x0F0F and 0xF0F0
+EDGE_MAC_L4 = ("tcp4", "udp4", "udp6", "arp")
+
+
+def with_byte(b: bytes, k: int, v: int) -> bytes:
+    return b[:k] + bytes([v]) + b[k + 1:]
+
+
+def _near(b: bytes) -> list[tuple[str, bytes]]:
+    """b with each single byte changed: its low bit flipped (^k) and the byte complemented (~k)."""
+    return [(f"^{k}", with_byte(b, k, b[k] ^ 0x01)) for k in range(len(b))] \
+        + [(f"~{k}", with_byte(b, k, b[k] ^ 0xFF)) for k in range(len(b))]
+
+
+def edge_macs() -> list[tuple[str, bytes]]:
+    """Destination MACs around the two that StackEthernet.Demux accepts (internet/stack-ethernet.go:146-152)."""
+    ones = b"\xff" * 6
+    out = [("us", MAC_US)] + [("us" + t, m) for t, m in _near(MAC_US)] + [("bcast", ones)]
+    out += [(f"bcast.fe{k}", with_byte(ones, k, 0xFE)) for k in range(6)]   # fe:ff:..: no group bit; ..:ff:fe: group bit
+    out += [(f"bcast.00{k}", with_byte(ones, k, 0x00)) for k in range(6)]
+    return out + [("zero", bytes(6)), ("mc4", bytes.fromhex("01005e000001")), ("mc6", bytes.fromhex("333300000001"))]
+
+
+def edge_ip4s() -> list[tuple[str, bytes]]:
+    """IPv4 destinations around demux4's rules (internet/stack-ip4.go:108-119, ipv4/definitions.go:17-36)."""
+    ones = b"\xff" * 4
+    out = [("us", IP4_DST)] + [("us" + t, a) for t, a in _near(IP4_DST)] + [("zero", bytes(4))]
+    out += [(".".join(map(str, a)), bytes(a)) for a in ((223, 255, 255, 255), (224, 0, 0, 0), (239, 255, 255, 255),
+                                                         (240, 0, 0, 0), (254, 255, 255, 255))]
+    out += [("bcast", ones)] + [(f"bcast.fe{k}", with_byte(ones, k, 0xFE)) for k in range(4)]
+    return out + [(nm, a) for nm, a in EDGE_IP4S.items()]
+
+
+def edge_ip6s() -> list[tuple[str, bytes]]:
+    """IPv6 destinations around demux6's rules (internet/stack-ip6.go:93-98, internal/ip.go:30-38)."""
+    out = [("us", IP6_DST)] + [("us" + t, a) for t, a in _near(IP6_DST)] + [("zero", bytes(16))]
+    for nm, head in (("ff00::", "ff00"), ("ff02::1", "ff02"), ("fe80::1", "fe80"), ("feff::1", "feff"), ("00ff::1", "00ff")):
+        out.append((nm, bytes.fromhex(head) + bytes(13) + bytes([0 if nm == "ff00::" else 1])))
+    return out + [(nm, a) for nm, a in EDGE_IP6S.items()]
+
+
+def filter_edge_frames(seed: int = 146) -> list[tuple[str, bytes]]:
+    """(label, frame) pairs for the comparisons behind the stack filter (lnx_rx_filter / oracle.StackFilter):
+    destinations one byte away from those the stack accepts, every IP protocol value on both IP versions and
+    EtherTypes around the size / type boundary.  Frames of 60-230 B with valid sums unless the variant says
+    otherwise, so the destination or handler decision alone sets the verdict; about a fifth carry a broken sum or
+    a size error besides, so a wrongly accepted frame shows another code than 0.  Deterministic.
+
+    label = <class>/<case>/<l4>/<variant>/<mac>:
+      mac/<case>/<tcp4|udp4|udp6|arp>/..: edge_macs() as the destination MAC (the IP destination is the stack's).
+      ip4/<case>/<tcp|udp>.ihl<5|7>/..: edge_ip4s() as the IPv4 destination, without options and behind 8 non-zero
+        option bytes (the destination stays at frame offset 30, the transport moves).
+      ip6/<case>/<tcp|udp>/..: edge_ip6s() as the IPv6 destination.
+      proto4/p<k>/<l4>/.., proto6/p<k>/<l4>/..: every protocol / next-header value 0..255; a correctly summed
+        TCP / UDP / ICMP echo / ICMPv6 echo where the reference sums one, 16 random bytes otherwise (`raw`; the
+        IPv4 ones once with a valid header sum and once with the TTL changed: a missing handler shows as
+        ErrPacketDrop only behind a header sum that passes).
+      et/<hex>/raw/..: EDGE_ETHERTYPES in front of 46 zero bytes.
+    variant: valid; l4flip (last transport byte), ttl (IPv4 header sum), cut1 (last byte missing).
+    mac: `-` in the mac class; else `us`, followed by the same frame as `tw<k>` with byte k of the destination
+      MAC changed (low bit and complement in turn), so every frame for the stack's MAC has a twin that is not."""
+    rng = np.random.default_rng(seed)
+    out = []
+    twins = [0]
+
+    def payload(lo=18, hi=150):
+        return rng.integers(0, 256, int(rng.integers(lo, hi)), dtype=np.uint8).tobytes()
+
+    def packet(l4, dst4=IP4_DST, dst6=IP6_DST, opts=b""):
+        if l4 == "tcp4":
+            return ether(0x0800, ipv4(6, tcp(payload()), opts=opts, dst=dst4))
+        if l4 == "udp4":
+            return ether(0x0800, ipv4(17, udp(payload()), opts=opts, dst=dst4))
+        if l4 == "tcp6":
+            return ether(0x86DD, ipv6(6, tcp(payload()), dst=dst6))
+        if l4 == "udp6":
+            return ether(0x86DD, ipv6(17, udp(payload()), dst=dst6))
+        return ether(0x0806, payload(28, 29) + bytes(18))  # ARP: 28 bytes and the padding to 60
+
+    def broken(f, variant):
+        b = bytearray(f)
+        if variant == "l4flip":
+            b[-1] ^= 1 << int(rng.integers(0, 8))
+        elif variant == "ttl":
+            b[22] ^= 0x01
+        elif variant == "cut1":
+            del b[-1]
+        return bytes(b)
+
+    def put(label, f, twin=True):
+        if not twin:
+            out.append((label + "/-", f))
+            return
+        out.append((label + "/us", f))
+        k, t = twins[0] % 6, twins[0]
+        twins[0] += 1
+        out.append((f"{label}/tw{k}", with_byte(f, k, f[k] ^ (0x01 if (t // 6) % 2 == 0 else 0xFF))))
+
+    def with_variants(tag, f, v4, i, twin=True):
+        """the valid frame and its broken forms: all of them for a destination the stack accepts
+        (us, bcast), one in rotation for every fifth of the others."""
+        put(f"{tag}/valid", f, twin)
+        forms = ("l4flip", "ttl", "cut1") if v4 else ("l4flip", "cut1")
+        if tag.split("/")[1] not in ("us", "bcast"):
+            forms = (forms[(i // 5) % len(forms)],) if i % 5 == 0 else ()
+        for v in forms:
+            put(f"{tag}/{v}", broken(f, v), twin)
+
+    i = 0
+    for case, m in edge_macs():
+        for l4 in EDGE_MAC_L4:
+            f = m + packet(l4)[6:]
+            if l4 == "arp":
+                put(f"mac/{case}/{l4}/valid", f, False)
+            else:
+                with_variants(f"mac/{case}/{l4}", f, l4.endswith("4"), i, False)
+            i += 1
+    for case, a in edge_ip4s():
+        for l4 in ("tcp", "udp"):
+            for ihl in (5, 7):
+                f = packet(l4 + "4", dst4=a, opts=opt_fill("rand", 4 * (ihl - 5), rng))
+                with_variants(f"ip4/{case}/{l4}.ihl{ihl}", f, True, i)
+                i += 1
+    for case, a in edge_ip6s():
+        for l4 in ("tcp", "udp"):
+            with_variants(f"ip6/{case}/{l4}", packet(l4 + "6", dst6=a), False, i)
+            i += 1
+    for p in range(256):
+        kind = {6: "tcp", 17: "udp", 1: "echo"}.get(p, "raw")
+        l4 = tcp(payload()) if p == 6 else udp(payload()) if p == 17 else icmp(8, payload()) if p == 1 \
+            else rng.integers(0, 256, 16, dtype=np.uint8).tobytes()
+        f = ether(0x0800, ipv4(p, l4))
+        f += bytes(max(0, 60 - len(f)))
+        put(f"proto4/p{p}/{kind}/valid", f)
+        put(f"proto4/p{p}/{kind}/" + ("ttl" if kind == "raw" else "l4flip"), broken(f, "ttl" if kind == "raw" else "l4flip"))
+    for p in range(256):
+        kind = {6: "tcp", 17: "udp", 58: "echo"}.get(p, "raw")
+        l4 = tcp(payload()) if p == 6 else udp(payload()) if p == 17 else icmp(128, payload()) if p == 58 \
+            else rng.integers(0, 256, 16, dtype=np.uint8).tobytes()
+        f = ether(0x86DD, ipv6(p, l4))
+        put(f"proto6/p{p}/{kind}/valid", f)
+        if kind != "raw":
+            put(f"proto6/p{p}/{kind}/l4flip", broken(f, "l4flip"))
+        elif p % 8 == 3:
+            put(f"proto6/p{p}/{kind}/cut1", broken(f, "cut1"))
+    for et in EDGE_ETHERTYPES:
+        put(f"et/{et:04x}/raw/valid", ether(et, bytes(46)))
+    return out

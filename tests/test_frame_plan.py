@@ -7,9 +7,9 @@ field through accessors over a heap copy of exactly the frame's bytes and takes
 the sums bytewise, in the kernels' little-endian half-word form at both address
 parities.  Here its receive verdicts must equal oracle.ingress_verdict on
 lneto's fuzz corpus (raw and fixed) and on every frame generator of the suite,
-under all four flag sets, without a filter and with two filters of
-tests/test_rx_filter.py.  The program is built a second time with
-AddressSanitizer and UBSan and run on the same input: an accessor called
+under all four flag sets, without a filter, with two filters of
+tests/test_rx_filter.py and three of tests/test_rx_filter_edges.py.  The
+program is built a second time with AddressSanitizer and UBSan and run on the same input: an accessor called
 outside its guard reads past the exact-size buffer."""
 import json
 import os
@@ -21,6 +21,7 @@ import pytest
 import lneto_amd as L
 from oracle import oracle as O
 from tests import framegen as G
+from tests.test_rx_filter_edges import FILTER_EDGES, frame_plan_subset
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "cpp", "frame_plan_host.cpp")
@@ -30,6 +31,9 @@ assert FLAGS == [0, 1, 2, 3]  # the program's flag loop
 FILTERS = [None,
            dict(ip4=G.IP4_DST, ip6=G.IP6_DST),
            dict(ip4=G.IP4_DST, ip6=G.IP6_DST, ethertypes=(0x0800, 0x88CC), ip4_protocols=(17, 47), ip6_protocols=(58,))]
+# ... and three of tests/test_rx_filter_edges.py: handlers in every mask word, all eight EtherType slots, a stack
+# address whose only non-zero byte is the last
+FILTERS += [FILTER_EDGES[name] for name in ("wide_handlers", "eight_types", "ip6_byte15")]
 
 
 def _spread(items, cap):
@@ -50,6 +54,8 @@ def frames():
     # every guard of the accessors: one UDP frame of each family cut at every length through its headers
     for whole in (G.ether(0x0800, G.ipv4(17, G.udp(b"guards"), opts=bytes(8))), G.ether(0x86DD, G.ipv6(17, G.udp(b"guards")))):
         out += [whole[:n] for n in range(len(whole))]
+    # near-miss destinations and the protocols at the mask words' edges (tests/framegen.py filter_edge_frames)
+    out += [f for _, f in frame_plan_subset(600)]
     return out
 
 
