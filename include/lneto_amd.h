@@ -459,6 +459,86 @@ int lnx_ingress_verify_batch_filtered(const uint8_t* d_bytes, const uint64_t* d_
 int lnx_rx_verify_batch(const uint8_t* d_bytes, const uint64_t* d_off, uint64_t n, uint32_t flags,
                         const lnx_rx_filter* filter, uint8_t* d_fcs_ok, uint8_t* d_verdict, void* stream);
 
+/* Receive delivery: the step after the verdict.  Once
+ * demux4 / demux6 have passed the transport sum they call the protocol
+ * handler's Demux (internet/stack-ip4.go:135-170, internet/stack-ip6.go:107-138);
+ * for TCP and UDP that handler is StackPorts.Demux
+ * (internet/stack-ports.go:64-84), which
+ *   returns io.ErrShortBuffer when the transport header holds no destination
+ *     port (:65-67; the library's 6, as lnx_fcs_append),
+ *   returns ErrPacketDrop when no node is registered on that port
+ *     (handlers.demuxByPort / nodeByPort, internet/definitions.go:108-116,141-152:
+ *     the FIRST node with that local port), and
+ *   for a TCP SYN without RST / ACK to such a port queues a RST (:70-82), unless
+ *     internal.GetIPAddr rejects the version nibble (internal/ip.go:9-27).
+ * A delivery record says, per frame, which handler it goes to or why not.
+ * Everything after the first call into that handler (TCP state, StackUDPPort's
+ * remote checks, DHCP / DNS / NTP) stays on the host. */
+#define LNX_H_ETH 0u      /* + index of the EtherType in filter->ethertypes (first match); + 8 with a NULL filter */
+#define LNX_H_IP4 16u     /* + IPv4 protocol, other than TCP / UDP */
+#define LNX_H_IP6 272u    /* + IPv6 next header, other than TCP / UDP */
+#define LNX_H_TCP 528u    /* + index of the port in ports->tcp (first match); + 256 with NULL ports */
+#define LNX_H_UDP 800u    /* + index of the port in ports->udp; + 256 with NULL ports */
+#define LNX_H_COUNT 1057u /* handler ids are below it; the bucket of the frames not delivered */
+#define LNX_H_NONE 0xFFFFu
+#define LNX_DLV_RST 1u    /* TCP miss that queues a RST (stack-ports.go:70-82): src_port, dst_port are filled */
+#define LNX_DLV_IP6 2u    /* the IP packet is IPv6 */
+#define LNX_DLV_FCS 4u    /* not delivered because its FCS is wrong (verdict 3) */
+typedef struct lnx_rx_delivery {
+  uint32_t ip_end;    /* end of the IP packet within the frame, 0 for non-IP / not reached */
+  uint16_t handler;   /* LNX_H_* id, LNX_H_NONE when not delivered */
+  uint16_t l4_off;    /* start of the transport header within the frame */
+  uint16_t src_port, dst_port;   /* filled whenever the port stage read them, the RST case included */
+  uint8_t verdict;    /* 0 delivered, else the errGeneric number (2 drop, 3 bad CRC, 6 short buffer, 18, ...) */
+  uint8_t flags;      /* LNX_DLV_* */
+  uint16_t zero;
+} lnx_rx_delivery;
+/* The nodes registered on StackPorts (Register, stack-ports.go:88-97) in
+ * registration order, per protocol; the same tables serve IPv4 and IPv6.
+ * Duplicates and port 0 are legal entries (first match).  n_* <= 256. */
+typedef struct lnx_rx_ports {
+  uint16_t tcp[256];
+  uint32_t n_tcp;
+  uint16_t udp[256];
+  uint32_t n_udp;
+} lnx_rx_ports;
+/* One frame on the host (len bytes, FCS stripped): verdict_in is its receive
+ * verdict (lnx_ingress_verdict, or what the batch entries gave), fcs_ok its FCS
+ * result (< 0: none).  In order: fcs_ok == 0 -> verdict 3 with LNX_DLV_FCS;
+ * verdict_in != 0 -> that verdict; else the handler by EtherType, IP protocol
+ * and port as above.  NULL filter: accept-all; NULL ports: every port has a
+ * handler (+ 256).  No read depends on verdict_in: a field the rules need at or
+ * past len, or an IP packet that ends past len, gives verdict 18; with a filter,
+ * an EtherType (other than IPv4 / IPv6) that it lists no handler for gives
+ * verdict 2 even under a zero verdict_in (demuxByProto finds no node).  Fields
+ * no rule reached are 0.  Returns LNX_OK, or LNX_EINVAL (NULL out, NULL frame with
+ * len > 0, a bad filter, n_tcp / n_udp > 256). */
+int lnx_rx_deliver(const uint8_t* frame, size_t len, const lnx_rx_filter* filter, const lnx_rx_ports* ports,
+                   int fcs_ok, uint8_t verdict_in, lnx_rx_delivery* out);
+/* The same for a batch on the device, chained behind lnx_rx_verify_batch /
+ * lnx_ingress_verify_batch[_filtered] on the same d_off (any order; an end below
+ * its start is an empty frame): frames carry their FCS and the record is that
+ * of the first max(len - 4, 0) bytes, unless flags has LNX_RX_NO_FCS (the only
+ * flag).  d_fcs_ok may be NULL (no FCS results).  d_rec[i] (16-byte aligned) is
+ * frame i's record.
+ * Grouping: d_order (n entries) is a permutation of 0..n-1, the frames by
+ * ascending handler id, the frames not delivered last (bucket LNX_H_COUNT), in
+ * ARRIVAL ORDER within every bucket (the segments of a connection keep their
+ * order); d_count[h] (LNX_H_COUNT + 1 entries) is the size of bucket h.  Both
+ * NULL: records only, d_ws is not touched; exactly one NULL: LNX_EINVAL.
+ * d_ws: lnx_rx_deliver_ws_bytes(n) bytes of the caller's device memory, 4-byte
+ * aligned, used by this call alone until its work on `stream` is done (no
+ * per-stream scratch of the library is involved).  n >= 2^32: LNX_EINVAL;
+ * n == 0: LNX_OK with d_count zeroed.  Asynchronous on `stream`; retains
+ * nothing and never synchronises the device.
+ * The receive ring (lnx_rx_ring_*, lnx_ingress_packets) does not run this step:
+ * it keeps returning fcs_ok / verdict only. */
+uint64_t lnx_rx_deliver_ws_bytes(uint64_t n);
+int lnx_rx_deliver_batch(const uint8_t* d_bytes, const uint64_t* d_off, uint64_t n, uint32_t flags,
+                         const lnx_rx_filter* filter, const lnx_rx_ports* ports, const uint8_t* d_fcs_ok,
+                         const uint8_t* d_verdict, lnx_rx_delivery* d_rec, uint32_t* d_order, uint32_t* d_count,
+                         void* d_ws, void* stream);
+
 /* pcap's checksum re-verification over a batch: d_status[i] =
  * lnx_pcap_checksums(d_bytes[d_off[i] : d_off[i+1]]) for every Ethernet frame
  * (FCS stripped; an end offset below its start is an empty frame).  Four

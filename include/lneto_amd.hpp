@@ -294,6 +294,51 @@ inline int VerifyIngressBatch(const uint8_t* d_frames, const uint64_t* d_off, ui
   if (!filter->ToC(&f)) return LNX_EINVAL;
   return lnx_ingress_verify_batch_filtered(d_frames, d_off, n, flags, &f, d_verdict, stream);
 }
+
+// The nodes registered on the TCP and UDP StackPorts (Register,
+// internet/stack-ports.go:88-97), by local port in registration order: what
+// handlers.nodeByPort walks (internet/definitions.go:108-116, first match).
+struct StackPortTables {
+  std::vector<uint16_t> TCP, UDP;
+
+  bool ToC(lnx_rx_ports* p) const {  // false for more than 256 nodes on a protocol
+    if (TCP.size() > 256 || UDP.size() > 256) return false;
+    *p = lnx_rx_ports{};
+    p->n_tcp = uint32_t(TCP.size()), p->n_udp = uint32_t(UDP.size());
+    for (size_t i = 0; i < TCP.size(); ++i) p->tcp[i] = TCP[i];
+    for (size_t i = 0; i < UDP.size(); ++i) p->udp[i] = UDP[i];
+    return true;
+  }
+};
+
+// Where the receive path hands one frame (FCS stripped) once its verdict is in:
+// the EtherType's handler, the IP protocol's, or for TCP / UDP the node
+// StackPorts.Demux finds on the destination port (internet/stack-ports.go:64-84:
+// io.ErrShortBuffer without a port, ErrPacketDrop without a node, LNX_DLV_RST
+// for the SYN it answers with a RST).  fcsOK < 0: no FCS result.  NULL
+// filter / ports: every EtherType, protocol and port has a handler.
+inline int Deliver(lneto::Bytes frame, uint8_t verdict, lnx_rx_delivery* out, const StackFilter* filter = nullptr,
+                   const StackPortTables* ports = nullptr, int fcsOK = -1) {
+  lnx_rx_filter f;
+  lnx_rx_ports p;
+  if ((filter && !filter->ToC(&f)) || (ports && !ports->ToC(&p))) return LNX_EINVAL;
+  return lnx_rx_deliver(frame.p, frame.n, filter ? &f : nullptr, ports ? &p : nullptr, fcsOK, verdict, out);
+}
+
+// The same for a batch on the device, behind VerifyIngressBatch or
+// lnx_rx_verify_batch on the same d_off; with d_order / d_count the frames
+// grouped by handler in arrival order (lnx_rx_deliver_batch; d_ws:
+// lnx_rx_deliver_ws_bytes(n) bytes of the caller's device memory).
+inline int DeliverBatch(const uint8_t* d_frames, const uint64_t* d_off, uint64_t n, const uint8_t* d_fcsOK,
+                        const uint8_t* d_verdict, lnx_rx_delivery* d_rec, uint32_t* d_order = nullptr,
+                        uint32_t* d_count = nullptr, void* d_ws = nullptr, const StackFilter* filter = nullptr,
+                        const StackPortTables* ports = nullptr, bool noFCS = false, void* stream = nullptr) {
+  lnx_rx_filter f;
+  lnx_rx_ports p;
+  if ((filter && !filter->ToC(&f)) || (ports && !ports->ToC(&p))) return LNX_EINVAL;
+  return lnx_rx_deliver_batch(d_frames, d_off, n, noFCS ? LNX_RX_NO_FCS : 0u, filter ? &f : nullptr,
+                              ports ? &p : nullptr, d_fcsOK, d_verdict, d_rec, d_order, d_count, d_ws, stream);
+}
 }  // namespace internet
 
 namespace netdev {

@@ -25,6 +25,8 @@ __all__ = [
     "sum_partial", "sum16_chain", "sum_partial_batch", "sum16_chain_batch",
     "crc32_batch_host", "crc32_batch_multi", "tx_checksum_batch", "rx_verify_batch", "device_count", "version", "build_id", "LIB_PATH",
     "CRC32_RESIDUE", "RxRing", "RxFilter", "RX_NO_FCS", "research_lib",
+    "RxPorts", "DELIVERY_DTYPE", "rx_deliver", "rx_deliver_batch", "rx_deliver_ws_bytes",
+    "H_ETH", "H_IP4", "H_IP6", "H_TCP", "H_UDP", "H_COUNT", "H_NONE", "DLV_RST", "DLV_IP6", "DLV_FCS",
 ]
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -97,6 +99,30 @@ class RxFilter(ctypes.Structure):
             for p in protos:
                 arr[p >> 3] |= 1 << (p & 7)
         return f
+
+
+class RxPorts(ctypes.Structure):
+    """lnx_rx_ports (include/lneto_amd.h): the local ports of the nodes registered
+    on StackPorts, per protocol and in registration order (Register,
+    internet/stack-ports.go:88-97; nodeByPort takes the first match,
+    internet/definitions.go:108-116).  Build it with RxPorts.make(tcp=..., udp=...)."""
+    _fields_ = [("tcp", ctypes.c_uint16 * 256), ("n_tcp", ctypes.c_uint32),
+                ("udp", ctypes.c_uint16 * 256), ("n_udp", ctypes.c_uint32)]
+
+    @classmethod
+    def make(cls, tcp=(), udp=()) -> "RxPorts":
+        tcp, udp = list(tcp), list(udp)
+        if len(tcp) > 256 or len(udp) > 256 or any(not 0 <= p <= 0xFFFF for p in tcp + udp):
+            raise LnetoError("RxPorts: at most 256 ports per protocol, each in [0, 0xFFFF]")
+        r = cls()
+        r.n_tcp, r.n_udp = len(tcp), len(udp)
+        for i, p in enumerate(tcp):
+            r.tcp[i] = p
+        for i, p in enumerate(udp):
+            r.udp[i] = p
+        return r
+
+
 _sig = {
     "lnx_crc32_update": (ctypes.c_uint32, [ctypes.c_uint32, _u8p, ctypes.c_size_t]),
     "lnx_crc32": (ctypes.c_uint32, [_u8p, ctypes.c_size_t]),
@@ -143,6 +169,11 @@ _sig = {
                                           ctypes.c_uint32, _vp]),
     "lnx_rx_verify_batch": (ctypes.c_int, [_vp, _vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.POINTER(RxFilter),
                                             _vp, _vp, _vp]),
+    "lnx_rx_deliver": (ctypes.c_int, [_vp, ctypes.c_size_t, ctypes.POINTER(RxFilter), ctypes.POINTER(RxPorts),
+                                      ctypes.c_int, ctypes.c_uint8, _vp]),
+    "lnx_rx_deliver_ws_bytes": (ctypes.c_uint64, [ctypes.c_uint64]),
+    "lnx_rx_deliver_batch": (ctypes.c_int, [_vp, _vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.POINTER(RxFilter),
+                                            ctypes.POINTER(RxPorts), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lnx_ingress_verdict": (ctypes.c_int, [_vp, ctypes.c_size_t, ctypes.c_uint32, ctypes.POINTER(RxFilter)]),
     "lnx_pcap_checksums": (ctypes.c_int, [_vp, ctypes.c_size_t]),
     "lnx_pcap_verify_batch": (ctypes.c_int, [_vp, _vp, ctypes.c_uint64, _vp, _vp]),
@@ -614,6 +645,80 @@ def rx_verify_batch(d_bytes, d_off, flags: int = 0, filter: RxFilter | None = No
                                            ctypes.byref(filter) if filter is not None else None, ok.data_ptr(),
                                            verdict.data_ptr(), s), what)
     return ok, verdict
+
+
+# Receive delivery (lnx_rx_deliver*): handler ids LNX_H_*, record flags LNX_DLV_*
+H_ETH, H_IP4, H_IP6, H_TCP, H_UDP, H_COUNT, H_NONE = 0, 16, 272, 528, 800, 1057, 0xFFFF
+DLV_RST, DLV_IP6, DLV_FCS = 1, 2, 4
+# lnx_rx_delivery as a numpy structured dtype (16 bytes): rec.cpu().numpy().view(DELIVERY_DTYPE).
+# None without numpy, which only this constant needs (torch brings it along).
+try:
+    import numpy as _np
+    DELIVERY_DTYPE = _np.dtype([("ip_end", "<u4"), ("handler", "<u2"), ("l4_off", "<u2"), ("src_port", "<u2"),
+                                ("dst_port", "<u2"), ("verdict", "u1"), ("flags", "u1"), ("zero", "<u2")])
+    assert DELIVERY_DTYPE.itemsize == 16
+except ImportError:  # pragma: no cover
+    DELIVERY_DTYPE = None
+
+
+def rx_deliver(frame: bytes, verdict_in: int, filter: RxFilter | None = None, ports: RxPorts | None = None,
+               fcs_ok: int | None = None) -> dict:
+    """The delivery record of ONE frame (FCS stripped) on the host (lnx_rx_deliver):
+    a dict of lnx_rx_delivery's fields.  verdict_in: the frame's receive verdict;
+    fcs_ok: its FCS result, None for none."""
+    buf = bytes(frame)
+    out = (ctypes.c_uint8 * 16)()
+    _check(lib.lnx_rx_deliver(buf, len(buf), ctypes.byref(filter) if filter is not None else None,
+                              ctypes.byref(ports) if ports is not None else None,
+                              -1 if fcs_ok is None else int(bool(fcs_ok)), verdict_in & 0xFF, ctypes.addressof(out)),
+           "lnx_rx_deliver")
+    raw = bytes(out)
+    ip_end = int.from_bytes(raw[0:4], "little")
+    handler, l4_off, src_port, dst_port = (int.from_bytes(raw[i:i + 2], "little") for i in (4, 6, 8, 10))
+    return dict(ip_end=ip_end, handler=handler, l4_off=l4_off, src_port=src_port, dst_port=dst_port,
+                verdict=raw[12], flags=raw[13], zero=int.from_bytes(raw[14:16], "little"))
+
+
+def rx_deliver_ws_bytes(n: int) -> int:
+    """Bytes of device workspace lnx_rx_deliver_batch needs to group n frames."""
+    return lib.lnx_rx_deliver_ws_bytes(n)
+
+
+def rx_deliver_batch(d_bytes, d_off, d_verdict, d_fcs_ok=None, flags: int = 0, filter: RxFilter | None = None,
+                     ports: RxPorts | None = None, group: bool = True, stream=None):
+    """Delivery records of a batch behind rx_verify_batch / ingress_verify_batch
+    on the same d_off (lnx_rx_deliver_batch): returns (rec, order, count).
+    rec is [n, 16] uint8, one lnx_rx_delivery a row (rec.cpu().numpy().view(DELIVERY_DTYPE));
+    with ``group`` order (int32, n) lists the frames by ascending handler id,
+    the frames not delivered last, in arrival order within every bucket, and
+    count (int32, H_COUNT + 1) the buckets' sizes; else both are None and no
+    workspace is allocated.  flags: RX_NO_FCS or 0 (frames carry their FCS)."""
+    import torch
+    what = "lnx_rx_deliver_batch"
+    b = _Batch(what, [("d_bytes", d_bytes, "u8"), ("d_off", d_off, "i64"), ("d_verdict", d_verdict, "u8"),
+                      ("d_fcs_ok", d_fcs_ok, "u8?")], stream)
+    n = d_off.numel() - 1
+    if n < 0:
+        raise LnetoError(f"{what}: d_off holds no offset")
+    _need_len(what, "d_verdict", d_verdict, n)
+    _need_len(what, "d_fcs_ok", d_fcs_ok, n)
+    rec = torch.empty((n, 16), dtype=torch.uint8, device=b.device)
+    order = count = ws = None
+    if group:
+        order = torch.empty(max(n, 1), dtype=torch.int32, device=b.device)  # (n = 0: still a pointer to pass)
+        count = torch.empty(H_COUNT + 1, dtype=torch.int32, device=b.device)
+        ws = torch.empty(rx_deliver_ws_bytes(n), dtype=torch.uint8, device=b.device)
+    with b as s:
+        _check(lib.lnx_rx_deliver_batch(d_bytes.data_ptr(), d_off.data_ptr(), n, flags,
+                                        ctypes.byref(filter) if filter is not None else None,
+                                        ctypes.byref(ports) if ports is not None else None,
+                                        d_fcs_ok.data_ptr() if d_fcs_ok is not None else None, d_verdict.data_ptr(),
+                                        rec.data_ptr(), order.data_ptr() if group else None,
+                                        count.data_ptr() if group else None, ws.data_ptr() if group else None, s),
+               what)
+        if ws is not None and stream is not None:
+            ws.record_stream(stream)  # freed on return: not to be reused before the stream is done with it
+    return rec, (order[:n] if group else None), count
 
 
 PCAP_IP_HDR_BAD, PCAP_PROTO_BAD = 1, 2  # LNX_PCAP_IP_HDR_BAD, LNX_PCAP_PROTO_BAD

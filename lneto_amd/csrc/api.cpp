@@ -37,6 +37,14 @@ hipError_t launch_sum_fold(const uint32_t* eo, const uint32_t* len, uint64_t nse
                            hipStream_t stream);
 }  // namespace lnxs
 
+// deliver_kernel.hip: receive delivery
+namespace lnxd {
+uint64_t deliver_ws_bytes(uint64_t n);
+hipError_t launch_deliver(const uint8_t* bytes, const uint64_t* off, uint64_t n, uint32_t trim, const lnx::RxFilter& filt,
+                          const lnx_rx_ports* ports, const uint8_t* fcs_ok, const uint8_t* verdict, lnx_rx_delivery* rec,
+                          uint32_t* order, uint32_t* count, void* ws, hipStream_t stream);
+}  // namespace lnxd
+
 namespace lnx {
 hipError_t launch_crc32_frames(const uint8_t* bytes, const uint64_t* off, uint64_t n, void* out,
                                bool verify, const void* image, int num_cus, hipStream_t stream, uint32_t policy,
@@ -874,6 +882,35 @@ int lnx_rx_verify_batch(const uint8_t* d_bytes, const uint64_t* d_off, uint64_t 
   return LNX_OK;
 }
 
+uint64_t lnx_rx_deliver_ws_bytes(uint64_t n) { return lnxd::deliver_ws_bytes(n); }
+
+// The workspace is the caller's: nothing here touches the per-stream scratch
+// sets and their epoch words (giant_scratch), and no device context is needed.
+int lnx_rx_deliver_batch(const uint8_t* d_bytes, const uint64_t* d_off, uint64_t n, uint32_t flags,
+                         const lnx_rx_filter* filter, const lnx_rx_ports* ports, const uint8_t* d_fcs_ok,
+                         const uint8_t* d_verdict, lnx_rx_delivery* d_rec, uint32_t* d_order, uint32_t* d_count,
+                         void* d_ws, void* stream) {
+  RxFilter filt;
+  if (!rx_filter_of(filter, &filt)) return LNX_EINVAL;
+  if (flags & ~(uint32_t)LNX_RX_NO_FCS) return LNX_EINVAL;
+  if (ports && (ports->n_tcp > 256u || ports->n_udp > 256u)) return LNX_EINVAL;
+  if ((d_order == nullptr) != (d_count == nullptr)) return LNX_EINVAL;
+  if (n >> 32) return LNX_EINVAL;
+  auto misaligned = [](const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; };
+  if (misaligned(d_rec, 16) || misaligned(d_order, 4) || misaligned(d_count, 4) || misaligned(d_ws, 4)) return LNX_EINVAL;
+  const hipStream_t hs = static_cast<hipStream_t>(stream);
+  if (n == 0) {
+    if (!d_count) return LNX_OK;
+    const hipError_t e = hipMemsetAsync(d_count, 0, (LNX_H_COUNT + 1u) * sizeof(uint32_t), hs);
+    return e == hipSuccess ? LNX_OK : hip_fail(e, "hipMemsetAsync(d_count)");
+  }
+  if (!d_bytes || !d_off || !d_verdict || !d_rec || (d_order && !d_ws)) return LNX_EINVAL;
+  const hipError_t e = lnxd::launch_deliver(d_bytes, d_off, n, (flags & LNX_RX_NO_FCS) ? 0u : 4u, filt, ports, d_fcs_ok,
+                                            d_verdict, d_rec, d_order, d_count, d_ws, hs);
+  if (e != hipSuccess) return hip_fail(e, "deliver kernels launch");
+  return LNX_OK;
+}
+
 int lnx_pcap_verify_batch(const uint8_t* d_bytes, const uint64_t* d_off, uint64_t n, uint8_t* d_status,
                           void* stream) {
   if (n == 0) return LNX_OK;
@@ -1062,7 +1099,9 @@ const char* lnx_version(void) {
          "48-frame groups) + zero copy through the ring's pinned slots + running CRCs (seeds, "
          "combine, frames made of segments: Z_k by nibble tables of x^(8 * 2^j) in LDS, a 16-lane row or the "
          "workgroup per frame) + running internet checksums (raw 32-bit sums at either byte phase, frames made of "
-         "segments: the sum16 line rows into E / O planes, a 16-lane row or the workgroup's four waves per frame)";
+         "segments: the sum16 line rows into E / O planes, a 16-lane row or the workgroup's four waves per frame) + "
+         "receive delivery (the port stage: a 16-lane row per frame, header bytes only, port tables in LDS; frames "
+         "grouped by handler in arrival order by a counting sort over contiguous slices)";
 }
 
 }  // extern "C"

@@ -55,6 +55,14 @@ __device__ __forceinline__ uint32_t row_xor16(uint32_t v) {
   v ^= (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x128, 0xF, 0xF, false);
   return v;
 }
+// The least value of each 16-lane row, in every lane of the row.
+__device__ __forceinline__ uint32_t row_min16(uint32_t v) {
+  v = min(v, (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xB1, 0xF, 0xF, false));
+  v = min(v, (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x4E, 0xF, 0xF, false));
+  v = min(v, (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x124, 0xF, 0xF, false));
+  v = min(v, (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x128, 0xF, 0xF, false));
+  return v;
+}
 // the XOR / sum over an 8-lane row (two quad steps, then the other quad of the half row)
 __device__ __forceinline__ uint32_t row_xor8(uint32_t v) {
   v ^= (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xB1, 0xF, 0xF, false);   // quad_perm [1,0,3,2]
