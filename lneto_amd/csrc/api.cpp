@@ -1,5 +1,6 @@
-// api.cpp — C-ABI of the batched HIP path: per-device context (the LDS table
-// image), argument checks, host-memory and multi-GPU conveniences.
+// api.cpp — C-ABI of the batched HIP path: per-device context (the table
+// images of table_images.cpp in device memory), argument checks, host-memory
+// and multi-GPU conveniences.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <atomic>
@@ -11,258 +12,12 @@
 #include <thread>
 #include <vector>
 #include "../../include/lneto_amd.h"
-#include "gf2.hpp"
-#include "lds_layout.hpp"
-#include "rx_filter.hpp"
 #include "dispatch.hpp"
-
-// crc32_combine_kernel.hip: the running-crc forms
-namespace lnxc {
-hipError_t launch_combine_pairs(const uint32_t* a, const uint32_t* b, const uint64_t* len, uint64_t n, uint32_t* out,
-                                int num_cus, hipStream_t stream);
-hipError_t launch_seed_pairs(const uint32_t* seed, const uint64_t* off, uint64_t n, uint32_t* crc, int num_cus,
-                             hipStream_t stream);
-hipError_t launch_chain_fold(const uint32_t* seg_crc, const uint32_t* len, uint64_t nseg, const uint64_t* first,
-                             uint64_t nframes, const uint32_t* seed, void* out, bool verify, int num_cus,
-                             hipStream_t stream);
-}  // namespace lnxc
-
-// sum16_chain_kernel.hip: the running internet checksums
-namespace lnxs {
-hipError_t launch_sum_bytes(const uint8_t* bytes, const uint64_t* off, const uint32_t* len, const uint32_t* seed,
-                            const uint8_t* phase, uint64_t n, uint32_t* out, bool planes, int num_cus,
-                            hipStream_t stream);
-hipError_t launch_sum_fold(const uint32_t* eo, const uint32_t* len, uint64_t nseg, const uint64_t* first,
-                           uint64_t nframes, const uint32_t* seed, uint16_t* out16, uint32_t* sum32, int num_cus,
-                           hipStream_t stream);
-}  // namespace lnxs
-
-// deliver_kernel.hip: receive delivery
-namespace lnxd {
-uint64_t deliver_ws_bytes(uint64_t n);
-hipError_t launch_deliver(const uint8_t* bytes, const uint64_t* off, uint64_t n, uint32_t trim, const lnx::RxFilter& filt,
-                          const lnx_rx_ports* ports, const uint8_t* fcs_ok, const uint8_t* verdict, lnx_rx_delivery* rec,
-                          uint32_t* order, uint32_t* count, void* ws, hipStream_t stream);
-}  // namespace lnxd
+#include "launch.hpp"
+#include "rx_filter.hpp"
+#include "table_images.hpp"
 
 namespace lnx {
-hipError_t launch_crc32_frames(const uint8_t* bytes, const uint64_t* off, uint64_t n, void* out,
-                               bool verify, const void* image, int num_cus, hipStream_t stream, uint32_t policy,
-                               uint32_t* stage_flag, uint32_t epoch);
-hipError_t launch_crc32_stage(const uint8_t* bytes, const uint64_t* off, uint64_t n, void* out, bool verify,
-                              uint32_t policy, const void* image, uint32_t* scratch, int num_cus, hipStream_t stream,
-                              const uint32_t* stage_flag, uint32_t epoch);
-#ifdef LNX_RESEARCH
-namespace rs {
-hipError_t launch_crc32_stage_research(const uint8_t* bytes, const uint64_t* off, uint64_t n, void* out, bool verify,
-                                       int fold, int waves, const void* image, int num_cus, hipStream_t stream,
-                                       bool big_blocks = false);
-}
-hipError_t launch_crc32_variant(int var, const uint8_t* bytes, const uint64_t* off, uint64_t n, void* out,
-                                const void* image, int num_cus, hipStream_t stream, uint64_t* timeline);
-uint64_t crc32_launch_waves(uint64_t n, int num_cus);
-hipError_t launch_fcs_scatter(uint8_t* bytes, const uint64_t* start, uint32_t* len, const uint32_t* crc, uint64_t n,
-                              uint32_t capacity, uint8_t* status, int num_cus, hipStream_t stream);
-#endif
-hipError_t launch_rx_verify(const uint8_t* bytes, const uint64_t* off, uint64_t n, uint32_t flags, bool fcs,
-                            uint8_t* ok, uint8_t* verdict, const uint32_t* seg_len, const RxFilter* filter,
-                            const uint32_t* image, int num_cus, hipStream_t stream, bool host = false,
-                            const uint32_t* gate = nullptr, uint32_t epoch = 0);
-hipError_t launch_pcap_verify(const uint8_t* bytes, const uint64_t* off, uint64_t n, uint8_t* status, int num_cus,
-                              hipStream_t stream);
-hipError_t launch_ingress_verify(const uint8_t* bytes, const uint64_t* off, uint64_t n, uint32_t flags,
-                                 uint8_t* verdict, int num_cus, hipStream_t stream, const uint32_t* seg_len,
-                                 uint32_t trim, const RxFilter* filter, uint32_t* gate = nullptr, uint32_t epoch = 0,
-                                 uint64_t short_mean = 0);
-hipError_t launch_crc32_search(const uint8_t* bytes, const uint64_t* off, const int64_t* min_off, uint64_t n,
-                               const uint32_t* tables, int64_t* result, int num_cus, hipStream_t stream);
-hipError_t launch_crc32_segments(const uint8_t* bytes, const uint64_t* start, const uint32_t* len, uint64_t n,
-                                 void* out, const void* images, int num_cus, hipStream_t stream);
-hipError_t launch_fcs_append(uint8_t* bytes, const uint64_t* start, uint32_t* len, uint64_t n, uint32_t capacity,
-                             uint8_t* status, const void* images, int num_cus, hipStream_t stream, int var = 0);
-hipError_t launch_tx_checksum(uint8_t* bytes, const uint64_t* start, const uint32_t* len, uint64_t n,
-                              uint8_t* status, int num_cus, hipStream_t stream, uint32_t* gate = nullptr,
-                              uint32_t epoch = 0, uint64_t short_mean = 0);
-hipError_t launch_tx_finish(uint8_t* bytes, const uint64_t* start, uint32_t* len, uint64_t n, uint32_t capacity,
-                            uint32_t flags, uint8_t* st_ck, uint8_t* st_ap, const uint32_t* image, int num_cus,
-                            hipStream_t stream, bool host, const uint32_t* gate = nullptr, uint32_t epoch = 0);
-hipError_t launch_sum16_segments(const uint8_t* bytes, const uint64_t* off, const uint32_t* len,
-                                 const uint32_t* seed, uint64_t n, uint16_t* out, int num_cus,
-                                 hipStream_t stream, int var = 0);
-
-// The 160 KiB LDS image of row width rl (lds_layout.hpp), built once on the host.
-std::vector<uint32_t> build_lds_image(uint32_t rl) {
-  std::vector<uint32_t> img(kLdsDwords, 0);
-  const int64_t sb = 4 * (int64_t)rl;
-  for (uint32_t m = 0; m < 4; ++m) {
-    for (uint32_t e = 0; e < 256; ++e) {
-      const uint32_t v = zshift_bytes(e << (8 * m), sb);  // U_m[e] = Z_SB(e << 8m)
-      for (uint32_t c = 0; c < 32; ++c) img[u_addr(m, e, c) / 4] = v;
-    }
-  }
-  for (uint32_t c = 0; c < 32; ++c) {
-    const int64_t p = c % rl;
-    for (uint32_t i = 0; i < 8; ++i)
-      for (uint32_t v = 0; v < 16; ++v)
-        img[f_addr(c, i, v) / 4] = zshift_bytes(v << (4 * i), -4 * p);  // F_p = Z_{-4p}
-    const uint32_t q0 = (uint32_t)p & 7u;
-    for (uint32_t h = 0; h < 2; ++h)
-      for (uint32_t t = 1; t < 4; ++t)
-        for (uint32_t v = 0; v < 16; ++v)
-          img[t_addr(c, h, t, v) / 4] = zshift_bytes(v << (4 * (q0 + 4 * h)), -(int64_t)t);  // Z_{-t}
-  }
-  return img;
-}
-
-#ifdef LNX_RESEARCH
-// The LDS image of the streaming rows (stream_rows.hpp) with row steps of SB
-// bytes (128: 8-lane rows, 64: 4-lane rows): U = Z_4 (the chain's dword step),
-// F column n = Z_{-4n} (n = 0..31), then the Z_{SB-12} byte tables (the skip
-// over the other lanes' pieces, at kSZ116), Z_c (c = 0..3) and Z_{SB-4k}
-// (k = 0..4) nibble tables by row lane, the constants Z_{SB-j}(0xFFFFFFFF) and
-// the Z_1 byte table.
-std::vector<uint32_t> build_stream_image(int64_t sb) {
-  std::vector<uint32_t> img(kLdsDwords, 0);
-  for (uint32_t m = 0; m < 4; ++m)
-    for (uint32_t e = 0; e < 256; ++e) {
-      const uint32_t v = zshift_bytes(e << (8 * m), 4);
-      for (uint32_t c = 0; c < 32; ++c) img[u_addr(m, e, c) / 4] = v;
-    }
-  for (uint32_t c = 0; c < 32; ++c)
-    for (uint32_t i = 0; i < 8; ++i)
-      for (uint32_t v = 0; v < 16; ++v) img[f_addr(c, i, v) / 4] = zshift_bytes(v << (4 * i), -4 * (int64_t)c);
-  for (uint32_t m = 0; m < 4; ++m)
-    for (uint32_t e = 0; e < 256; ++e) img[(kSZ116 + 1024 * m + 4 * e) / 4] = zshift_bytes(e << (8 * m), sb - 12);
-  for (uint32_t c = 0; c < 4; ++c)
-    for (uint32_t p = 0; p < 8; ++p)
-      for (uint32_t v = 0; v < 16; ++v) img[kSTc / 4 + (c * 8 + p) * 16 + v] = zshift_bytes(v << (4 * p), c);
-  for (uint32_t k = 0; k < 5; ++k)
-    for (uint32_t p = 0; p < 8; ++p)
-      for (uint32_t v = 0; v < 16; ++v)
-        img[kSG / 4 + (k * 8 + p) * 16 + v] = zshift_bytes(v << (4 * p), sb - 4 * (int64_t)k);
-  for (uint32_t j = 0; j < 16; ++j) img[kSK / 4 + j] = zshift_bytes(0xFFFFFFFFu, sb - (int64_t)j);
-  for (uint32_t e = 0; e < 256; ++e) img[kST1 / 4 + e] = zshift_bytes(e, 1);
-  return img;
-}
-
-// The LDS image of the lane streams (stream_lanes.hpp): U = Z_4, then the
-// Z_c byte tables (c = 1..3), the Z_{64-4k} nibble tables (k = 0..15) and
-// the constants Z_{64-j}(0xFFFFFFFF) (lds_layout.hpp kLZc, kLZd, kLK).
-std::vector<uint32_t> build_lanes_image() {
-  std::vector<uint32_t> img(kLdsDwords, 0);
-  for (uint32_t m = 0; m < 4; ++m)
-    for (uint32_t e = 0; e < 256; ++e) {
-      const uint32_t v = zshift_bytes(e << (8 * m), 4);
-      for (uint32_t c = 0; c < 32; ++c) img[u_addr(m, e, c) / 4] = v;
-    }
-  for (uint32_t c = 1; c < 4; ++c)
-    for (uint32_t m = 0; m < 4; ++m)
-      for (uint32_t e = 0; e < 256; ++e) img[kLZc / 4 + (c - 1) * 1024 + 256 * m + e] = zshift_bytes(e << (8 * m), c);
-  for (uint32_t k = 0; k < 16; ++k)
-    for (uint32_t i = 0; i < 8; ++i)
-      for (uint32_t v = 0; v < 16; ++v)
-        img[kLZd / 4 + 128 * k + 16 * i + v] = zshift_bytes(v << (4 * i), 64 - 4 * (int64_t)k);
-  for (uint32_t j = 0; j < 64; ++j) img[kLK / 4 + j] = zshift_bytes(0xFFFFFFFFu, 64 - (int64_t)j);
-  return img;
-}
-#endif  // LNX_RESEARCH
-
-// The staged lane streams' image (stage_kernel.hip): the slicing-by-2 byte
-// tables A[e] = Z_2(e), B[e] = Z_1(e), then Z_{2^m} as eight nibble tables
-// for m = 0..30, entry (m, i, v) at dword 512 + 128 m + 16 i + v.
-std::vector<uint32_t> build_stage_image() {
-  std::vector<uint32_t> t(512 + 31 * 128 + 1024 + 2048 + 3 * 1024 + 4 * 1024 + 9 * 128);
-  for (uint32_t e = 0; e < 256; ++e) t[e] = zshift_bytes(e, 2), t[256 + e] = zshift_bytes(e, 1);
-  for (uint32_t m = 0; m < 31; ++m)
-    for (uint32_t i = 0; i < 8; ++i)
-      for (uint32_t v = 0; v < 16; ++v) t[512 + 128 * m + 16 * i + v] = zshift_bytes_fast(v << (4 * i), 1ull << m);
-  for (uint32_t k = 0; k < 4; ++k)  // Z_4 byte tables (the FOLD 4 variants)
-    for (uint32_t e = 0; e < 256; ++e) t[512 + 31 * 128 + 256 * k + e] = zshift_bytes(e << (8 * k), 4);
-  for (uint32_t k = 0; k < 8; ++k)  // slicing-by-8 byte tables T8_k[e] = Z_{8-k}(e) (the FOLD 8 variants)
-    for (uint32_t e = 0; e < 256; ++e) t[512 + 31 * 128 + 1024 + 256 * k + e] = zshift_bytes(e, 8 - (int)k);
-  for (uint32_t z = 0; z < 3; ++z)  // Z_16, Z_32, Z_64 byte tables (the deferred-correction variants)
-    for (uint32_t k = 0; k < 4; ++k)
-      for (uint32_t e = 0; e < 256; ++e)
-        t[512 + 31 * 128 + 1024 + 2048 + 1024 * z + 256 * k + e] = zshift_bytes(e << (8 * k), 16 << z);
-  for (uint32_t z = 0; z < 4; ++z)  // Z_8, Z_16, Z_24, Z_32 byte tables (two chains per half)
-    for (uint32_t k = 0; k < 4; ++k)
-      for (uint32_t e = 0; e < 256; ++e)
-        t[512 + 31 * 128 + 1024 + 2048 + 3 * 1024 + 1024 * z + 256 * k + e] = zshift_bytes(e << (8 * k), 8 * (z + 1));
-  for (uint32_t m = 31; m < 40; ++m)  // Z_{2^m} nibble tables for m = 31..39 (giant frames' Z_d, stage_kernel.hip)
-    for (uint32_t i = 0; i < 8; ++i)
-      for (uint32_t v = 0; v < 16; ++v)
-        t[512 + 31 * 128 + 1024 + 2048 + 3 * 1024 + 4 * 1024 + 128 * (m - 31) + 16 * i + v] =
-            zshift_bytes_fast(v << (4 * i), 1ull << m);
-  return t;
-}
-
-// The fused receive kernel's image (rx_verify_kernel.hip): the slicing tables
-// T_k[e] = Z_128(e << 8k), T_{4+k}[e] = Z_124(e << 8k) (k < 4), then the nibble
-// tables of Z_{-8q} (q < 32) and Z_{-b} (b < 8), entry (t, i, v) at 128 t + 16 i + v.
-std::vector<uint32_t> build_rx_image() {
-  std::vector<uint32_t> t(2048 + 56 * 128);
-  for (uint32_t k = 0; k < 4; ++k)
-    for (uint32_t e = 0; e < 256; ++e) {
-      t[256 * k + e] = zshift_bytes(e << (8 * k), 128);
-      t[256 * (4 + k) + e] = zshift_bytes(e << (8 * k), 124);
-    }
-  for (uint32_t q = 0; q < 40; ++q)
-    for (uint32_t i = 0; i < 8; ++i)
-      for (uint32_t v = 0; v < 16; ++v)
-        t[2048 + 128 * q + 16 * i + v] = zshift_bytes(v << (4 * i), q < 32 ? -8 * (int64_t)q : -(int64_t)(q - 32));
-  // then Z_{2^m}, m < 16: the transmit kernel's CRC corrections for the fields it writes
-  for (uint32_t m = 0; m < 16; ++m)
-    for (uint32_t i = 0; i < 8; ++i)
-      for (uint32_t v = 0; v < 16; ++v) t[2048 + 40 * 128 + 128 * m + 16 * i + v] = zshift_bytes(v << (4 * i), 1ll << m);
-  return t;
-}
-
-// Tables of crc32_search_kernel: the byte-step table, then Z_{4*2^k} as four
-// byte tables for k = 0..5 (search_kernel.hip).
-// Then the tables of crc32_search_seg_kernel (24-byte lane segments): the
-// byte-step table replicated in 32 bank columns (entry e, column c at 32e + c),
-// Z_{24*2^k} as four byte tables for k = 0..5, and Z_4 as four byte tables;
-// then Z_{48*2^k} for k = 0..4 (crc32_search_half_kernel, 48-byte segments).
-std::vector<uint32_t> build_search_tables() {
-  constexpr uint32_t kOld = 256 + 6 * 1024, kSeg = 24;  // = kSearchSeg
-  std::vector<uint32_t> t(kOld + 8192 + 7 * 1024 + 5 * 1024 + 4096 + 1024 + 4096 + 3 * 1024);
-  for (uint32_t e = 0; e < 256; ++e) t[e] = zshift_bytes(e, 1);
-  for (uint32_t k = 0; k < 6; ++k)
-    for (uint32_t m = 0; m < 4; ++m)
-      for (uint32_t e = 0; e < 256; ++e) t[256 + k * 1024 + m * 256 + e] = zshift_bytes(e << (8 * m), 4 << k);
-  for (uint32_t e = 0; e < 256; ++e)
-    for (uint32_t c = 0; c < 32; ++c) t[kOld + 32 * e + c] = t[e];
-  for (uint32_t k = 0; k < 6; ++k)
-    for (uint32_t m = 0; m < 4; ++m)
-      for (uint32_t e = 0; e < 256; ++e)
-        t[kOld + 8192 + k * 1024 + m * 256 + e] = zshift_bytes_fast(e << (8 * m), (uint64_t)kSeg << k);
-  for (uint32_t m = 0; m < 4; ++m)  // Z_4 (slicing-by-4) for the segment folds
-    for (uint32_t e = 0; e < 256; ++e) t[kOld + 8192 + 6 * 1024 + m * 256 + e] = zshift_bytes(e << (8 * m), 4);
-  // crc32_search_half_kernel (48-byte segments): Z_{48*2^k} for k = 0..4
-  for (uint32_t k = 0; k < 5; ++k)
-    for (uint32_t m = 0; m < 4; ++m)
-      for (uint32_t e = 0; e < 256; ++e)
-        t[kOld + 8192 + 7 * 1024 + k * 1024 + m * 256 + e] = zshift_bytes_fast(e << (8 * m), (uint64_t)48 << k);
-  // Z_4 as eight nibble tables, each entry in 32 bank columns: (i, v, c) at (16 i + v) * 32 + c
-  for (uint32_t i = 0; i < 8; ++i)
-    for (uint32_t v = 0; v < 16; ++v)
-      for (uint32_t c = 0; c < 32; ++c)
-        t[kOld + 8192 + 12 * 1024 + (16 * i + v) * 32 + c] = zshift_bytes(v << (4 * i), 4);
-  // Z_24 as four byte tables (crc32_search_u_kernel's split chains: half a 48-byte segment)
-  for (uint32_t m = 0; m < 4; ++m)
-    for (uint32_t e = 0; e < 256; ++e) t[kOld + 8192 + 12 * 1024 + 4096 + m * 256 + e] = zshift_bytes(e << (8 * m), 24);
-  // octet segments (crc32_search_o_kernel): Z_48 as eight nibble tables in 32
-  // bank columns, (i, v, c) at (16 i + v) * 32 + c, then Z_{192*2^k}, k = 0..2
-  constexpr uint32_t kOct = kOld + 8192 + 12 * 1024 + 4096 + 1024;
-  for (uint32_t i = 0; i < 8; ++i)
-    for (uint32_t v = 0; v < 16; ++v)
-      for (uint32_t c = 0; c < 32; ++c) t[kOct + (16 * i + v) * 32 + c] = zshift_bytes_fast(v << (4 * i), 48);
-  for (uint32_t k = 0; k < 3; ++k)
-    for (uint32_t m = 0; m < 4; ++m)
-      for (uint32_t e = 0; e < 256; ++e)
-        t[kOct + 4096 + k * 1024 + m * 256 + e] = zshift_bytes_fast(e << (8 * m), (uint64_t)192 << k);
-  return t;
-}
 
 namespace {
 
@@ -326,39 +81,6 @@ struct DeviceCtx {
 constexpr int kMaxDevices = 64;
 DeviceCtx g_ctx[kMaxDevices];
 
-// Compact form of an image (lds_layout.hpp kCompactDwords): the U values once,
-// then the F/T tail verbatim.
-std::vector<uint32_t> compact_image(const std::vector<uint32_t>& full) {
-  std::vector<uint32_t> c(kCompactDwords);
-  for (uint32_t m = 0; m < 4; ++m)
-    for (uint32_t e = 0; e < 256; ++e) c[256 * m + e] = full[u_addr(m, e, 0) / 4];
-  std::copy(full.begin() + kFBase / 4, full.end(), c.begin() + kCompactUDwords);
-  return c;
-}
-
-// The compact images back to back: [RL = 16][RL = 4][RL = 32][stream][stream64][lanes] (lds_layout.hpp image_index).
-const std::vector<uint32_t>& host_image() {
-  static const std::vector<uint32_t> img = [] {
-    std::vector<uint32_t> all;
-#ifdef LNX_RESEARCH
-    for (uint32_t rl : {16u, 4u, 32u, 8u, 9u, 10u}) {  // 8, 9: the stream images (128- and 64-byte row steps); 10: lanes
-      const std::vector<uint32_t> im = compact_image(rl == 8    ? build_stream_image(128)
-                                                     : rl == 9  ? build_stream_image(64)
-                                                     : rl == 10 ? build_lanes_image()
-                                                                : build_lds_image(rl));
-      all.insert(all.end(), im.begin(), im.end());
-    }
-#else
-    for (uint32_t rl : {16u, 4u, 32u}) {  // the product's row widths (image_index 0..2)
-      const std::vector<uint32_t> im = compact_image(build_lds_image(rl));
-      all.insert(all.end(), im.begin(), im.end());
-    }
-#endif
-    return all;
-  }();
-  return img;
-}
-
 // Context of the calling thread's current device (created on first use).  A
 // failed initialization (e.g. hipMalloc out of memory) frees what it had
 // allocated and leaves the context uninitialized, so a later call retries.
@@ -374,28 +96,20 @@ int init_ctx(DeviceCtx& c, int dev) {
     c.d_rx = nullptr;
     return hip_fail(err, what);
   };
-  hipError_t err = hipDeviceGetAttribute(&c.num_cus, hipDeviceAttributeMultiprocessorCount, dev);
+  const hipError_t err = hipDeviceGetAttribute(&c.num_cus, hipDeviceAttributeMultiprocessorCount, dev);
   if (err != hipSuccess) return fail(err, "hipDeviceGetAttribute");
-  const auto& img = host_image();
-  if ((err = hipMalloc(&c.d_image, img.size() * 4)) != hipSuccess) return fail(err, "hipMalloc(image)");
-  if ((err = hipMemcpy(c.d_image, img.data(), img.size() * 4, hipMemcpyHostToDevice)) != hipSuccess)
-    return fail(err, "hipMemcpy(image)");
-  const std::vector<uint32_t> st = build_search_tables();
-  if ((err = hipMalloc(reinterpret_cast<void**>(&c.d_search), st.size() * 4)) != hipSuccess)
-    return fail(err, "hipMalloc(search tables)");
-  if ((err = hipMemcpy(c.d_search, st.data(), st.size() * 4, hipMemcpyHostToDevice)) != hipSuccess)
-    return fail(err, "hipMemcpy(search tables)");
-  const std::vector<uint32_t> sg = build_stage_image();
-  if ((err = hipMalloc(reinterpret_cast<void**>(&c.d_stage), sg.size() * 4)) != hipSuccess)
-    return fail(err, "hipMalloc(stage image)");
-  if ((err = hipMemcpy(c.d_stage, sg.data(), sg.size() * 4, hipMemcpyHostToDevice)) != hipSuccess)
-    return fail(err, "hipMemcpy(stage image)");
-  const std::vector<uint32_t> rx = build_rx_image();
-  if ((err = hipMalloc(reinterpret_cast<void**>(&c.d_rx), rx.size() * 4)) != hipSuccess)
-    return fail(err, "hipMalloc(rx image)");
-  if ((err = hipMemcpy(c.d_rx, rx.data(), rx.size() * 4, hipMemcpyHostToDevice)) != hipSuccess)
-    return fail(err, "hipMemcpy(rx image)");
-  return LNX_OK;
+  // one table image into device memory of its own
+  auto upload = [&](auto** dst, const std::vector<uint32_t>& img, const std::string& name) {
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(dst), img.size() * 4);
+    if (e != hipSuccess) return fail(e, ("hipMalloc(" + name + ")").c_str());
+    e = hipMemcpy(*dst, img.data(), img.size() * 4, hipMemcpyHostToDevice);
+    return e == hipSuccess ? LNX_OK : fail(e, ("hipMemcpy(" + name + ")").c_str());
+  };
+  int st = upload(&c.d_image, host_image(), "image");
+  if (st == LNX_OK) st = upload(&c.d_search, build_search_tables(), "search tables");
+  if (st == LNX_OK) st = upload(&c.d_stage, build_stage_image(), "stage image");
+  if (st == LNX_OK) st = upload(&c.d_rx, build_rx_image(), "rx image");
+  return st;
 }
 
 int get_ctx(DeviceCtx** out) {
@@ -503,14 +217,12 @@ int giant_scratch(DeviceCtx* c, hipStream_t stream, ScratchHold* hold) {
   return LNX_OK;
 }
 
-}  // namespace
-
 // CRC-32 / FCS verify of an offsets batch: the rows kernel,
 // then the staged kernel, over the same slices; each workgroup folds its slice
 // only if dispatch.hpp's slice_kind() gives it to its kernel, and the staged
 // launch folds the giant slices.  policy kPolicyShort (LNX_BATCH_SHORT_FRAMES)
 // gives every slice that fits to the staged kernel, so the rows launch is
-// skipped.  Also the receive ring's entry (rx_ring.hip).
+// skipped.  The plain and _ex entries below are its only callers.
 int crc_offsets(const uint8_t* d_bytes, const uint64_t* d_off, uint64_t n, void* d_out, bool verify, uint32_t policy,
                 hipStream_t stream) {
   DeviceCtx* c = nullptr;
@@ -533,7 +245,6 @@ int crc_offsets(const uint8_t* d_bytes, const uint64_t* d_off, uint64_t n, void*
   return LNX_OK;
 }
 
-namespace {
 int crc_common(const uint8_t* d_bytes, const uint64_t* d_off, uint64_t n, void* d_out, bool verify,
                uint32_t flags, void* stream) {
   if (flags & ~LNX_BATCH_SHORT_FRAMES) return LNX_EINVAL;
@@ -544,8 +255,8 @@ int crc_common(const uint8_t* d_bytes, const uint64_t* d_off, uint64_t n, void* 
 }
 }  // namespace
 
-// For the other translation units (rx_ring.hip): the current device's LDS
-// image and CU count, and the thread's lnx_last_error.
+// For rx_ring.hip (launch.hpp): the current device's images and CU count, and
+// the thread's lnx_last_error.
 int device_resources(const void** image, int* num_cus, const void** stage_image, const void** rx_image) {
   DeviceCtx* c = nullptr;
   int st = get_ctx(&c);

@@ -25,6 +25,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include "gf2.hpp"
+#include "launch.hpp"
 #include "wave_util.hpp"
 
 namespace lnxc {

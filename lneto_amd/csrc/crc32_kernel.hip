@@ -48,6 +48,7 @@
 #include <utility>
 #include "lds_layout.hpp"
 #include "dispatch.hpp"
+#include "launch.hpp"
 #include "wave_util.hpp"
 
 // Cache-policy suffix of the streaming frame loads (e.g. " nt" for profiling

@@ -16,6 +16,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include "deliver_plan.hpp"
+#include "launch.hpp"
 #include "rx_filter.hpp"
 #include "wave_util.hpp"
 

@@ -14,6 +14,7 @@
 #include <cstdint>
 #include <cstring>
 #include "../../include/lneto_amd.h"
+#include "host_path.hpp"
 #include "rx_filter.hpp"
 
 namespace lnx {

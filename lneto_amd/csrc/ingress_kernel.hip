@@ -20,6 +20,7 @@
 #include <cstdlib>
 #include <type_traits>
 #include "frame_plan.hpp"
+#include "launch.hpp"
 #include "rx_filter.hpp"
 #include "wave_util.hpp"
 

@@ -32,6 +32,7 @@
 // the loads never fault.
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include "launch.hpp"
 #include "wave_util.hpp"
 
 namespace lnx {

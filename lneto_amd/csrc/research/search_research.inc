@@ -10,7 +10,7 @@ crc32_search_kernel(const uint8_t* __restrict__ bytes, const uint64_t* __restric
                     const int64_t* __restrict__ min_off, uint64_t n, const uint32_t* __restrict__ tables,
                     int64_t* __restrict__ result) {
   __shared__ uint32_t lds[kSearchTabBytes / 4];
-  for (uint32_t i = threadIdx.x; i < kSearchTabBytes / 4; i += kSearchBlock) lds[i] = tables[i];
+  for (uint32_t i = threadIdx.x; i < kWordTabDwords; i += kSearchBlock) lds[i] = tables[kWordStepOff + i];
   __syncthreads();
   const uint32_t lane = threadIdx.x & 63u;
   const uint64_t nwaves = (uint64_t)gridDim.x * (kSearchBlock / 64);

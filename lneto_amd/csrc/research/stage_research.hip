@@ -44,6 +44,8 @@
 #ifdef LNX_RESEARCH
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include "../launch.hpp"
+#include "../table_layout.hpp"
 
 namespace lnx {
 namespace rs {
@@ -79,17 +81,7 @@ struct StageLds {
   static constexpr uint32_t kBytes = kCtr + 16;
   static_assert(kBytes <= 163840, "stage LDS");
 };
-// compact image in HBM (api.cpp build_stage_image): A[256], B[256], then the
-// nibble tables verbatim (512 + 31 * 128 dwords), then (FOLD 4) the four Z_4
-// byte tables, table k entry e at kStageZ4Img + 256 k + e
-constexpr uint32_t kStageZ4Img = 512 + 31 * 128;
-// then (FOLD 8) the eight slicing-by-8 byte tables T8_k[e] = Z_{8-k}(e), table
-// k entry e at kStageZ8Img + 256 k + e
-constexpr uint32_t kStageZ8Img = kStageZ4Img + 1024;
-// then (DEFER) Z_16, Z_32, Z_64 as four byte tables each: (t, k, e) at kStageZxImg + 1024 t + 256 k + e
-constexpr uint32_t kStageZxImg = kStageZ8Img + 2048;
-// then (two chains per half) Z_8, Z_16, Z_24, Z_32: (t, k, e) at kStageZyImg + 1024 t + 256 k + e = Z_{8(t+1)}(e << 8k)
-constexpr uint32_t kStageZyImg = kStageZxImg + 3072;
+// (the image in HBM: table_layout.hpp kStageAImg .. kStageZyImg)
 
 constexpr uint32_t kSOOB = 0x80000000u;
 constexpr uint32_t kSNone = 0xFFFFFFFFu;
@@ -183,7 +175,7 @@ __device__ __forceinline__ uint32_t s_z4(const char* lds, uint32_t v, uint32_t b
 
 // Z_{2^m}(v) through the shared nibble tables (every lane reads table m: a
 // nibble value picks one of 16 banks, equal values broadcast), from LDS or,
-// for W > 8, from the image in HBM (dword (m, i, v) at 512 + 128 m + 16 i + v)
+// for W > 8, from the image in HBM (table_layout.hpp stage_nib)
 template <class LY>
 __device__ __forceinline__ uint32_t s_zpow2(const char* lds, const uint32_t* image, uint32_t m, uint32_t v) {
   uint32_t a = 0;
@@ -192,9 +184,9 @@ __device__ __forceinline__ uint32_t s_zpow2(const char* lds, const uint32_t* ima
 #pragma unroll
     for (uint32_t i = 0; i < 8; ++i) a ^= s_lds(lds, t + 64u * i + (__builtin_amdgcn_ubfe(v, 4 * i, 4) << 2));
   } else {
-    const uint32_t* t = image + 512u + 128u * m;
+    const uint32_t* t = image + kStageNibImg + kNib8Dwords * m;
 #pragma unroll
-    for (uint32_t i = 0; i < 8; ++i) a ^= t[16u * i + __builtin_amdgcn_ubfe(v, 4 * i, 4)];
+    for (uint32_t i = 0; i < 8; ++i) a ^= t[nib8_at(0, i, __builtin_amdgcn_ubfe(v, 4 * i, 4))];
   }
   return a;
 }
@@ -253,7 +245,7 @@ crc32_stage_rs_kernel(const uint8_t* __restrict__ bytes, const uint64_t* __restr
       }
     } else {
       for (uint32_t vi = t; vi < 512u; vi += kThreads) {
-        const uint32_t v = image[vi];
+        const uint32_t v = image[kStageAImg + vi];  // A, then B
         const uint32_t m = vi >> 8, e = vi & 255u;
         uint4* row = reinterpret_cast<uint4*>(lds + kSTab + (e << 8) + (m << 7));
         const uint4 v4 = {v, v, v, v};
@@ -262,8 +254,8 @@ crc32_stage_rs_kernel(const uint8_t* __restrict__ bytes, const uint64_t* __restr
       }
     }
     if constexpr (LY::kNibInLds)
-      for (uint32_t i = t; i < 31u * 128u; i += kThreads)
-        reinterpret_cast<uint32_t*>(lds + LY::kNib)[i] = image[512 + i];
+      for (uint32_t i = t; i < kStageNibLo * kNib8Dwords; i += kThreads)
+        reinterpret_cast<uint32_t*>(lds + LY::kNib)[i] = image[kStageNibImg + i];
     if constexpr (LY::kZxBytes != 0)
       for (uint32_t i = t; i < LY::kZxBytes / 4u; i += kThreads)
         reinterpret_cast<uint32_t*>(lds + LY::kZx)[i] = image[(DEFER ? kStageZxImg : kStageZyImg) + i];

@@ -24,7 +24,9 @@
 #include <cstdint>
 #include <type_traits>
 #include "frame_plan.hpp"
+#include "launch.hpp"
 #include "rx_filter.hpp"
+#include "table_layout.hpp"
 #include "wave_util.hpp"
 
 namespace lnx {
@@ -55,8 +57,7 @@ constexpr int kRvUnroll = 12;  // qwords per lane per batch (1536 bytes per row,
 // 8 bank columns (e << 8 | k << 5 | c << 2), then F_q = Z_{-8q} (q < 32) and B_b = Z_{-b} (b < 8) as
 // nibble tables, entry (t, i, v) at 128 t + 16 i + v dwords
 constexpr uint32_t kRvT = 0, kRvF = 65536, kRvB = kRvF + 32 * 512, kRvBytes = kRvB + 8 * 512;
-// the compact image (api.cpp build_rx_image): T_k[e] at 256 k + e, then F, then B (dwords)
-constexpr uint32_t kRvImgF = 2048;  // (then B at kRvImgF + 32 * 128; 2048 + 40 * 128 dwords in all)
+// (the image in HBM: table_layout.hpp kRvImgT, kRvImgF, kRvImgB, kTxImgP)
 
 // A qword load through the global address space: the pointer is a select of
 // a frame address and g_rv_zero, which hipcc would otherwise load with a FLAT
@@ -611,7 +612,7 @@ rx_verify_kernel(const uint8_t* __restrict__ bytes, const uint64_t* __restrict__
   if constexpr (CRC) {
     const uint32_t t = threadIdx.x;
     for (uint32_t vi = t; vi < 2048u; vi += kRvBlock) {
-      const uint32_t v = image[vi];
+      const uint32_t v = image[kRvImgT + vi];
       uint4* row = reinterpret_cast<uint4*>(lds + kRvT + ((vi & 255u) << 8) + ((vi >> 8) << 5));
       const uint4 v4 = {v, v, v, v};
       row[0] = v4;
@@ -622,7 +623,7 @@ rx_verify_kernel(const uint8_t* __restrict__ bytes, const uint64_t* __restrict__
     for (uint32_t i = t; i < 32u * 128u; i += kRvBlock)
       reinterpret_cast<uint32_t*>(lds + kRvF)[32u * (i & 127u) + (i >> 7)] = image[kRvImgF + i];
     for (uint32_t i = t; i < 8u * 128u; i += kRvBlock)
-      reinterpret_cast<uint32_t*>(lds + kRvB)[i] = image[kRvImgF + 32u * 128u + i];
+      reinterpret_cast<uint32_t*>(lds + kRvB)[i] = image[kRvImgB + i];
     __syncthreads();
   }
   const uint32_t trim = CRC ? 4u : 0u;
@@ -810,7 +811,6 @@ rx_verify_kernel(const uint8_t* __restrict__ bytes, const uint64_t* __restrict__
 // (0, or 6 ErrShortBuffer with the frame left unpadded).
 constexpr uint32_t kTxP = kRvBytes;                    // Z_{2^m} nibble tables in LDS (after F, B)
 constexpr uint32_t kTxTabBytes = kRvBytes + 16u * 512u;
-constexpr uint32_t kTxImgP = kRvImgF + 40u * 128u;     // ... and in the image
 
 // Z_k(x), k < 2^16, by binary powers (the steps some lane of the wave needs)
 __device__ __forceinline__ uint32_t tx_zk(const char* lds, uint32_t k, uint32_t x) {
@@ -877,7 +877,7 @@ tx_finish_kernel(uint8_t* __restrict__ bytes, const uint64_t* __restrict__ start
   if constexpr (FCS) {
     const uint32_t t = threadIdx.x;
     for (uint32_t vi = t; vi < 2048u; vi += kB) {
-      const uint32_t v = image[vi];
+      const uint32_t v = image[kRvImgT + vi];
       uint4* row = reinterpret_cast<uint4*>(lds + kRvT + ((vi & 255u) << 8) + ((vi >> 8) << 5));
       const uint4 v4 = {v, v, v, v};
       row[0] = v4;
@@ -886,7 +886,7 @@ tx_finish_kernel(uint8_t* __restrict__ bytes, const uint64_t* __restrict__ start
     for (uint32_t i = t; i < 32u * 128u; i += kB)
       reinterpret_cast<uint32_t*>(lds + kRvF)[32u * (i & 127u) + (i >> 7)] = image[kRvImgF + i];
     for (uint32_t i = t; i < 8u * 128u; i += kB)
-      reinterpret_cast<uint32_t*>(lds + kRvB)[i] = image[kRvImgF + 32u * 128u + i];
+      reinterpret_cast<uint32_t*>(lds + kRvB)[i] = image[kRvImgB + i];
     for (uint32_t i = t; i < 16u * 128u; i += kB) reinterpret_cast<uint32_t*>(lds + kTxP)[i] = image[kTxImgP + i];
     __syncthreads();
   }

@@ -23,11 +23,13 @@
 #include <cstdint>
 #include <cstdlib>
 #include "gf2.hpp"
+#include "launch.hpp"
+#include "table_layout.hpp"
 
 namespace lnx {
 
 [[maybe_unused]] constexpr int kSearchBlock = 256;
-[[maybe_unused]] constexpr uint32_t kSearchTabBytes = 1024 + 6 * 4096;  // byte-step table + 6 x 4 byte tables
+[[maybe_unused]] constexpr uint32_t kSearchTabBytes = 4 * kWordTabDwords;  // byte-step table + 6 x 4 byte tables
 constexpr uint32_t kResidueRegister = 0xDEBB20E3u;     // ~0x2144DF1C
 
 // Z_{4*2^k}(x) through the four byte tables of level k
@@ -52,8 +54,7 @@ __device__ __forceinline__ uint32_t zlevel(const uint32_t* lds, int k, uint32_t 
 // realigned with v_alignbyte (a dword holding a capture byte never crosses a
 // page, so loads stop at the capture end).
 constexpr uint32_t kSearchSeg = 24;  // 1536-byte blocks: a 1500-B capture keeps 63 of 64 lanes busy
-constexpr uint32_t kSegTabOff = 256 + 6 * 1024;                  // after the word-lane kernel's tables
-constexpr uint32_t kSegTabDwords = 8192 + 7 * 1024;              // replicated byte table + 6 levels + Z_4
+// (table_layout.hpp kSegTabOff, kSegTabDwords: the replicated byte table, 6 levels and Z_4, also the LDS layout)
 constexpr int kSegBlock = 1024;  // 2 blocks per CU (57 KiB LDS each): 8 waves per SIMD
 
 __device__ __forceinline__ uint32_t zseg(const uint32_t* z, uint32_t x) {  // four byte tables at z
@@ -191,9 +192,7 @@ crc32_search_seg_kernel(const uint8_t* __restrict__ bytes, const uint64_t* __res
 // levels of Z_{48*2^k}.  Per byte that is 0.42 scan lookups (shared tables,
 // bank-conflicting) against 1.0 with 24-byte segments over 64 lanes.
 constexpr uint32_t kHalfSeg = 48;
-constexpr uint32_t kHalfTabOff = kSegTabOff + kSegTabDwords;  // Z_{48*2^k}, k = 0..4, in the host tables
 constexpr uint32_t kHalfLdsDwords = 8192 + 5 * 1024 + 1024;    // byte table (32 columns), 5 levels, Z_4
-constexpr uint32_t kHalfNibOff = kHalfTabOff + 5 * 1024;         // Z_4 nibble tables in 32 columns (4096 dwords)
 //
 // Pass B by word checks (WB, the r2 product): the register after k = 1..4
 // bytes of a word entered with register r is Z_k(r ^ (w & lo_k)), lo_k the
@@ -216,7 +215,6 @@ static_assert(kResBack4 == 0xFFFFFFFFu && kResBack1 == 0x00BE26EDu, "residue bac
 // four waves per SIMD are enough (r2y: the byte-chain pass B was latency-bound
 // in this layout).
 constexpr uint32_t kULdsDwords = 32768 + 6 * 1024;  // U (Z_4, 32 columns), Z_{48*2^k} for k = 0..4, Z_24
-constexpr uint32_t kZ24Off = kHalfNibOff + 4096;     // Z_24 byte tables in the host tables
 __device__ __forceinline__ uint32_t ulds(const uint32_t* lds, uint32_t byte_addr) {
   return *reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(lds) + byte_addr);
 }
@@ -242,7 +240,7 @@ __device__ __forceinline__ void search_half_body(uint32_t* lds, const uint8_t* _
   if constexpr (UL) {
     // thread t expands Z_4 value t (table t >> 8, entry t & 255) into its 32 bank replicas
     static_assert(kSegBlock == 1024, "one U value per thread");
-    const uint32_t t = threadIdx.x, v = tables[kSegTabOff + 8192 + 6 * 1024 + t];
+    const uint32_t t = threadIdx.x, v = tables[kSegZ4Off + t];
     const uint32_t ua = ((t >> 9) << 16) | ((t & 255u) << 8) | (((t >> 8) & 1u) << 7);
     uint4* row = reinterpret_cast<uint4*>(reinterpret_cast<char*>(lds) + ua);
     const uint4 v4 = {v, v, v, v};
@@ -251,7 +249,7 @@ __device__ __forceinline__ void search_half_body(uint32_t* lds, const uint8_t* _
   } else {
     for (uint32_t i = threadIdx.x; i < kNib; i += kSegBlock) lds[kHalfLdsDwords + i] = tables[kHalfNibOff + i];
     for (uint32_t i = threadIdx.x; i < 8192; i += kSegBlock) lds[i] = tables[kSegTabOff + i];
-    for (uint32_t i = threadIdx.x; i < 1024; i += kSegBlock) lds[8192 + 5 * 1024 + i] = tables[kSegTabOff + 8192 + 6 * 1024 + i];
+    for (uint32_t i = threadIdx.x; i < 1024; i += kSegBlock) lds[8192 + 5 * 1024 + i] = tables[kSegZ4Off + i];
   }
   for (uint32_t i = threadIdx.x; i < 5 * 1024; i += kSegBlock) lds[kZt + i] = tables[kHalfTabOff + i];
   __syncthreads();
@@ -427,7 +425,7 @@ __device__ __forceinline__ void search_u_body(uint32_t* lds, const uint8_t* __re
   constexpr uint32_t SEG = kHalfSeg, NW = SEG / 4;
   {
     static_assert(kSegBlock == 1024, "one U value per thread");
-    const uint32_t t = threadIdx.x, v = tables[kSegTabOff + 8192 + 6 * 1024 + t];
+    const uint32_t t = threadIdx.x, v = tables[kSegZ4Off + t];
     const uint32_t ua = ((t >> 9) << 16) | ((t & 255u) << 8) | (((t >> 8) & 1u) << 7);
     uint4* row = reinterpret_cast<uint4*>(reinterpret_cast<char*>(lds) + ua);
     const uint4 v4 = {v, v, v, v};
@@ -701,8 +699,6 @@ crc32_search_u_kernel(const uint8_t* __restrict__ bytes, const uint64_t* __restr
 // in 32 bank columns).  A lane keeps its smallest valid hit byte; the first
 // lane of its octet with a hit gives the capture's answer (lanes are in byte
 // order).  tests/test_search_algebra.py::oct_search restates the schedule.
-constexpr uint32_t kOctNibOff = kZ24Off + 1024;          // host tables: Z_48 nibble tables, 32 columns
-[[maybe_unused]] constexpr uint32_t kOctLevOff = kOctNibOff + 4096;  // host tables: Z_{192*2^k}, k = 0..2 (copied with the nibbles)
 constexpr uint32_t kOctLdsDwords = 32768 + 4096 + 3 * 1024;
 static_assert(kOctLdsDwords * 4 <= 163840, "octet LDS");
 
@@ -715,14 +711,14 @@ crc32_search_o_kernel(const uint8_t* __restrict__ bytes, const uint64_t* __restr
   __shared__ __attribute__((aligned(16))) uint32_t lds[kOctLdsDwords];
   {
     static_assert(kSegBlock == 1024, "one U value per thread");
-    const uint32_t t = threadIdx.x, v = tables[kSegTabOff + 8192 + 6 * 1024 + t];
+    const uint32_t t = threadIdx.x, v = tables[kSegZ4Off + t];
     const uint32_t ua = ((t >> 9) << 16) | ((t & 255u) << 8) | (((t >> 8) & 1u) << 7);
     uint4* row = reinterpret_cast<uint4*>(reinterpret_cast<char*>(lds) + ua);
     const uint4 v4 = {v, v, v, v};
 #pragma unroll
     for (int i = 0; i < 8; ++i) row[(i + t) & 7u] = v4;
   }
-  for (uint32_t i = threadIdx.x; i < 4096u + 3u * 1024u; i += kSegBlock) lds[32768 + i] = tables[kOctNibOff + i];
+  for (uint32_t i = threadIdx.x; i < kOctTabDwords; i += kSegBlock) lds[32768 + i] = tables[kOctNibOff + i];
   __syncthreads();
   const uint32_t lane = threadIdx.x & 63u, col = lane & 31u, hl = lane & (LPC - 1), oct = lane / LPC;
   const uint32_t* zt = lds + 32768 + 4096;  // Z_{192*2^k} at zt + 1024 k (shared)

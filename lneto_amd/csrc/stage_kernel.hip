@@ -43,6 +43,8 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include "dispatch.hpp"
+#include "launch.hpp"
+#include "table_layout.hpp"
 
 namespace lnx {
 
@@ -64,13 +66,7 @@ constexpr uint32_t kSBad = kSGpre + 260 * 4;            // giant slices out of o
 constexpr uint32_t kSBytes = kSBad + 32;
 static_assert(kSBytes <= 163840, "stage LDS");
 static_assert((kStageBF + 2) % 64 == 0, "whole-wave list loads");
-// compact image in HBM (api.cpp build_stage_image): A[256], B[256], the
-// nibble tables of Z_{2^m} for m = 0..30 (512 + 128 m + 16 i + v), the Z_4
-// byte tables, the slicing-by-8 byte tables T8_k[e] = Z_{8-k}(e) at
-// kStageZ8Img + 256 k + e, the research tables, then the nibble tables of
-// Z_{2^m} for m = 31..39 at kStageNibHiImg + 128 (m - 31) + 16 i + v
-constexpr uint32_t kStageZ8Img = 512 + 31 * 128 + 1024;
-constexpr uint32_t kStageNibHiImg = kStageZ8Img + 2048 + 3072 + 4096;
+// (the image in HBM: table_layout.hpp kStageZ8Img, kStageNibImg, kStageNibHiImg)
 // giant slices: pieces of at least this many bytes, at most kGiantPieces of them
 constexpr uint64_t kGiantPieceMin = 16384;
 constexpr uint32_t kGiantPieces = 1u << 20;
@@ -149,10 +145,10 @@ __device__ __forceinline__ uint32_t s_zd64(const char* lds, const uint32_t* imag
     if (m <= 30) {
       z = s_zpow2(lds, m, v);
     } else {
-      const uint32_t* t = image + kStageNibHiImg + 128u * (m - 31u);
+      const uint32_t* t = image + kStageNibHiImg + kNib8Dwords * (m - kStageNibLo);
       z = 0;
 #pragma unroll
-      for (uint32_t i = 0; i < 8; ++i) z ^= t[16u * i + __builtin_amdgcn_ubfe(v, 4 * i, 4)];
+      for (uint32_t i = 0; i < 8; ++i) z ^= t[nib8_at(0, i, __builtin_amdgcn_ubfe(v, 4 * i, 4))];
     }
     v = ((d >> m) & 1u) ? z : v;
   }
@@ -595,7 +591,8 @@ crc32_stage_kernel(const uint8_t* __restrict__ bytes, const uint64_t* __restrict
       row[0] = v4;
       row[1] = v4;
     }
-    for (uint32_t i = t; i < 31u * 128u; i += kThreads) reinterpret_cast<uint32_t*>(lds + kSNib)[i] = image[512 + i];
+    for (uint32_t i = t; i < kStageNibLo * kNib8Dwords; i += kThreads)
+      reinterpret_cast<uint32_t*>(lds + kSNib)[i] = image[kStageNibImg + i];
     if (t == 0) *reinterpret_cast<uint32_t*>(lds + kSCtr) = 0;
     if (t < 8u) reinterpret_cast<uint32_t*>(lds + kSBad)[t] = 0;
   }

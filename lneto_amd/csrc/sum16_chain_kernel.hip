@@ -17,6 +17,7 @@
 // The row helpers shared with sum16_kernel.hip are wave_util.hpp's.
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include "launch.hpp"
 #include "wave_util.hpp"
 
 namespace lnxs {

@@ -17,6 +17,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <cstdlib>
+#include "launch.hpp"
 #include "wave_util.hpp"
 
 namespace lnx {

@@ -1,5 +1,5 @@
 // rows_emulator.cpp — CPU emulation of one row of crc32_rows_kernel, lane by
-// lane, reading the real LDS images that liblneto_amd builds (api.cpp
+// lane, reading the real LDS images that liblneto_amd builds (table_images.cpp
 // build_lds_image) at the byte addresses the kernel uses.  Checks the window
 // geometry (aligned window end, lead-in mask, init fold and its spill, junk
 // removal, F_p, row XOR, Z_{-t} fix) against a plain table CRC-32 for every
@@ -14,10 +14,8 @@
 #include <cstring>
 #include <vector>
 #include "../../lneto_amd/csrc/lds_layout.hpp"
+#include "../../lneto_amd/csrc/table_images.hpp"
 
-namespace lnx {
-std::vector<uint32_t> build_lds_image(uint32_t rl);
-}
 using namespace lnx;
 
 static uint32_t crc_tab[256];
