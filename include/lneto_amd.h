@@ -670,7 +670,15 @@ int lnx_ingress_packets(lnx_rx_ring* ring, const uint8_t* const* bufs, const uin
  * kernel patches them in place in the slots: they may then already be padded
  * and carry their FCS while their lens are stale.  Zero copy is taken for a
  * batch only when every frame's room [offset, offset + capacity) lies inside
- * one slot and no slot holds two of the batch's frames.  lnx_ingress_packets
+ * one slot and no slot holds two of the batch's frames.  "The batch" is the
+ * internal batch of `batch_slots` consecutive frames (frames [k * batch_slots,
+ * (k + 1) * batch_slots) of the call), not the call: a batch that is refused
+ * takes the copying form (gathered, finished on the device, written back)
+ * while the call's other batches may still be patched in place; the results
+ * are the same either way.  An argument error (LNX_EINVAL: capacity >
+ * slot_cap, lens[k] > capacity, an unknown flag, a NULL buffer with a length
+ * or, under LNX_TX_FCS, at all) is found before anything is written: lens,
+ * status and the buffers are then left as they were.  lnx_ingress_packets
  * writes results the same way. */
 #define LNX_TX_CHECKSUM 1u
 #define LNX_TX_FCS 2u

@@ -418,7 +418,10 @@ int lnx_rx_ring_ingress(lnx_rx_ring* r, uint32_t first, uint32_t count, uint32_t
   hipError_t e = hipSetDevice(r->device);
   if (e != hipSuccess) return hip_error(e, "hipSetDevice");
   int rc = LNX_OK;
-  std::vector<bool> packed_pending(r->depth, false);  // stage k's staging is in use by its last batch
+  // stage k's staging (h_pack / h_off) was packed and handed to async copies
+  // on its stream, and that stream has not been synchronized since: a batch
+  // in between that does not use the staging (whole slots) leaves it busy
+  std::vector<bool> packed_pending(r->depth, false);
   uint32_t k = 0;
   for (uint32_t b0 = first; b0 < first + count && rc == LNX_OK; b0 += r->batch, ++k) {
     const uint32_t nb = std::min(r->batch, first + count - b0);
@@ -446,8 +449,8 @@ int lnx_rx_ring_ingress(lnx_rx_ring* r, uint32_t first, uint32_t count, uint32_t
         break;
       }
       pack_batch(s, nb, [&](uint32_t j) { return r->h_slots + (size_t)(b0 + j) * r->cap + offset; }, flen);
+      packed_pending[k % r->depth] = true;
     }
-    packed_pending[k % r->depth] = pack;
     rc = enqueue_rx(r, s, nb, pack ? RxSrc::kPacked : RxSrc::kSlotsCopy, b0, offset, flags, r->h_ok + b0,
                     r->h_verdict + b0);
   }
@@ -599,7 +602,8 @@ int lnx_egress_packets(lnx_rx_ring* r, uint8_t* const* bufs, uint32_t* lens, uin
       uint64_t pos = 0;
       direct = in_ring(r, bufs[i0 + j], offset, capacity, &pos);
       const uint64_t rel = pos - offset, slot = rel / r->cap;
-      direct = direct && rel % r->cap + offset + capacity <= r->cap && slot_batch[slot] != k + 1;
+      // (an empty room at the very end of slot memory has no slot: slot == nslots)
+      direct = direct && slot < r->nslots && rel % r->cap + offset + capacity <= r->cap && slot_batch[slot] != k + 1;
       if (direct) slot_batch[slot] = k + 1;
       s.h_off[j] = pos;
       s.h_len[j] = lens[i0 + j];
