@@ -531,13 +531,36 @@ int lnx_rx_deliver(const uint8_t* frame, size_t len, const lnx_rx_filter* filter
  * per-stream scratch of the library is involved).  n >= 2^32: LNX_EINVAL;
  * n == 0: LNX_OK with d_count zeroed.  Asynchronous on `stream`; retains
  * nothing and never synchronises the device.
- * The receive ring (lnx_rx_ring_*, lnx_ingress_packets) does not run this step:
- * it keeps returning fcs_ok / verdict only. */
+ * The receive ring runs this step in lnx_rx_ring_ingress_deliver and
+ * lnx_ingress_packets_deliver (below), from the same read as its receive check;
+ * lnx_rx_ring_ingress and lnx_ingress_packets keep returning fcs_ok / verdict
+ * only. */
 uint64_t lnx_rx_deliver_ws_bytes(uint64_t n);
 int lnx_rx_deliver_batch(const uint8_t* d_bytes, const uint64_t* d_off, uint64_t n, uint32_t flags,
                          const lnx_rx_filter* filter, const lnx_rx_ports* ports, const uint8_t* d_fcs_ok,
                          const uint8_t* d_verdict, lnx_rx_delivery* d_rec, uint32_t* d_order, uint32_t* d_count,
                          void* d_ws, void* stream);
+
+/* The receive check and the delivery records from ONE read of each frame
+ * (DESIGN.md §3.18): d_fcs_ok and d_verdict are, byte for byte, what
+ * lnx_rx_verify_batch(d_bytes, d_off, n, flags, filter, ...) writes, and d_rec /
+ * d_order / d_count what lnx_rx_deliver_batch writes when chained behind it with
+ * those two arrays, the same filter and ports and flags & LNX_RX_NO_FCS.  flags:
+ * LNX_VERIFY_EVIL_BIT, LNX_VERIFY_ICMP, LNX_RX_NO_FCS.  d_off in any order.  The
+ * receive kernel's lane that holds a frame's FCS result and verdict applies the
+ * delivery rules to the header bytes it has staged (past them, for IPv4 options,
+ * to the frame's own aligned words), so the header lines are read once; the
+ * grouping is the three grouping launches of lnx_rx_deliver_batch on the keys
+ * that kernel wrote.  d_order and d_count both NULL: records only, d_ws is not
+ * touched; exactly one NULL: LNX_EINVAL.  d_ws: lnx_rx_deliver_ws_bytes(n) bytes,
+ * as above.  n == 0: LNX_OK with d_count zeroed.  n >= 2^32, NULL d_rec (or
+ * d_fcs_ok / d_verdict), a bad filter, n_tcp / n_udp > 256: LNX_EINVAL.
+ * Asynchronous on `stream`; retains nothing, never synchronises the device and
+ * uses none of the library's per-stream scratch. */
+int lnx_rx_verify_deliver_batch(const uint8_t* d_bytes, const uint64_t* d_off, uint64_t n, uint32_t flags,
+                                const lnx_rx_filter* filter, const lnx_rx_ports* ports, uint8_t* d_fcs_ok,
+                                uint8_t* d_verdict, lnx_rx_delivery* d_rec, uint32_t* d_order, uint32_t* d_count,
+                                void* d_ws, void* stream);
 
 /* pcap's checksum re-verification over a batch: d_status[i] =
  * lnx_pcap_checksums(d_bytes[d_off[i] : d_off[i+1]]) for every Ethernet frame
@@ -648,6 +671,34 @@ int lnx_rx_ring_ingress(lnx_rx_ring* ring, uint32_t first, uint32_t count, uint3
  * plus 8 bytes of offset per frame; nothing is retained after the call. */
 int lnx_ingress_packets(lnx_rx_ring* ring, const uint8_t* const* bufs, const uint32_t* lens, uint64_t n,
                         uint32_t offset, uint32_t flags, uint8_t* fcs_ok, uint8_t* verdict);
+
+/* Receive delivery through the ring.  lnx_rx_ring_set_ports
+ * gives the ring the StackPorts tables for it (a copy is kept; NULL, the
+ * default: every port has a handler, + 256); n_tcp / n_udp > 256: LNX_EINVAL.
+ * lnx_rx_ring_ingress_deliver and lnx_ingress_packets_deliver are
+ * lnx_rx_ring_ingress and lnx_ingress_packets (the same routing, host threshold,
+ * statistics and error behaviour) whose receive check also writes rec[k], frame
+ * k's lnx_rx_delivery under the ring's filter and ports, from the same read of
+ * the frame: on the zero-copy routes the header lines cross PCIe once.  rec is
+ * required (host memory, count / n entries); fcs_ok and verdict may be NULL;
+ * order (count / n entries) and count_out (LNX_H_COUNT + 1 entries) are both
+ * given or both NULL (exactly one: LNX_EINVAL, nothing written).  They cover
+ * the whole call as lnx_rx_deliver_batch's d_order / d_count would: every
+ * internal batch is grouped on the device in its stage's pipeline, and the
+ * call's order is the stable concatenation of those groups — for every bucket
+ * in ascending order, and for the batches in arrival order, the batch's run of
+ * that bucket — so arrival order holds within every bucket.  Below the host
+ * threshold the records come from lnx_rx_deliver per frame and the groups from
+ * a stable counting sort on the host.  The buffers these entries need are
+ * allocated by the first of them (or lnx_rx_ring_set_ports) to be called; a
+ * ring that never calls them allocates nothing for them. */
+int lnx_rx_ring_set_ports(lnx_rx_ring* ring, const lnx_rx_ports* ports);
+int lnx_rx_ring_ingress_deliver(lnx_rx_ring* ring, uint32_t first, uint32_t count, uint32_t offset, uint32_t flags,
+                                uint8_t* fcs_ok, uint8_t* verdict, lnx_rx_delivery* rec, uint32_t* order,
+                                uint32_t* count_out);
+int lnx_ingress_packets_deliver(lnx_rx_ring* ring, const uint8_t* const* bufs, const uint32_t* lens, uint64_t n,
+                                uint32_t offset, uint32_t flags, uint8_t* fcs_ok, uint8_t* verdict,
+                                lnx_rx_delivery* rec, uint32_t* order, uint32_t* count_out);
 
 /* netdev.Stack.EgressPackets(bufs, sizes, offset) (x/netdev/interface.go:85;
  * xnet.Netstack.EgressPackets, x/xnet/netstack.go:87-98) for the device's part

@@ -339,6 +339,20 @@ inline int DeliverBatch(const uint8_t* d_frames, const uint64_t* d_off, uint64_t
   return lnx_rx_deliver_batch(d_frames, d_off, n, noFCS ? LNX_RX_NO_FCS : 0u, filter ? &f : nullptr,
                               ports ? &p : nullptr, d_fcsOK, d_verdict, d_rec, d_order, d_count, d_ws, stream);
 }
+
+// VerifyIngressBatch-with-FCS and DeliverBatch from one read of each frame
+// (lnx_rx_verify_deliver_batch): d_fcsOK / d_verdict as lnx_rx_verify_batch
+// writes them, d_rec / d_order / d_count as DeliverBatch behind it.
+inline int VerifyDeliverBatch(const uint8_t* d_frames, const uint64_t* d_off, uint64_t n, uint8_t* d_fcsOK,
+                              uint8_t* d_verdict, lnx_rx_delivery* d_rec, uint32_t* d_order = nullptr,
+                              uint32_t* d_count = nullptr, void* d_ws = nullptr, const StackFilter* filter = nullptr,
+                              const StackPortTables* ports = nullptr, uint32_t flags = 0, void* stream = nullptr) {
+  lnx_rx_filter f;
+  lnx_rx_ports p;
+  if ((filter && !filter->ToC(&f)) || (ports && !ports->ToC(&p))) return LNX_EINVAL;
+  return lnx_rx_verify_deliver_batch(d_frames, d_off, n, flags, filter ? &f : nullptr, ports ? &p : nullptr, d_fcsOK,
+                                     d_verdict, d_rec, d_order, d_count, d_ws, stream);
+}
 }  // namespace internet
 
 namespace netdev {
@@ -402,6 +416,27 @@ class RxRing {
     ptrs_.clear();  // unpinned: nothing refers to the caller's buffers after the call
     lens_.clear();
     return rc;
+  }
+  // The StackPorts tables of the deliver entries (nullptr: every port has a handler).
+  int SetPorts(const internet::StackPortTables* t) {
+    if (!t) return lnx_rx_ring_set_ports(r_, nullptr);
+    lnx_rx_ports c;
+    if (!t->ToC(&c)) return LNX_EINVAL;
+    return lnx_rx_ring_set_ports(r_, &c);
+  }
+  // Ingress / IngressPackets with each frame's delivery record from the same
+  // read (rec required; order and count both given or both nullptr: the
+  // call's frames grouped by handler in arrival order, LNX_H_COUNT + 1 counts).
+  int IngressDeliver(uint32_t first, uint32_t count, uint32_t offset, uint8_t* fcsOK, uint8_t* verdict,
+                     lnx_rx_delivery* rec, uint32_t* order = nullptr, uint32_t* countOut = nullptr,
+                     bool evilBit = false) {
+    return lnx_rx_ring_ingress_deliver(r_, first, count, offset, flags(evilBit), fcsOK, verdict, rec, order, countOut);
+  }
+  int IngressPacketsDeliver(const uint8_t* const* bufs, const uint32_t* lens, uint64_t n, uint32_t offset,
+                            uint8_t* fcsOK, uint8_t* verdict, lnx_rx_delivery* rec, uint32_t* order = nullptr,
+                            uint32_t* countOut = nullptr, bool evilBit = false) {
+    return lnx_ingress_packets_deliver(r_, bufs, lens, n, offset, flags(evilBit), fcsOK, verdict, rec, order,
+                                       countOut);
   }
   // netdev.Stack.EgressPackets(bufs, sizes, offset) (x/netdev/interface.go:85)
   // for the device's part of the transmit path: frame k = bufs[k][offset :

@@ -25,7 +25,7 @@ __all__ = [
     "sum_partial", "sum16_chain", "sum_partial_batch", "sum16_chain_batch",
     "crc32_batch_host", "crc32_batch_multi", "tx_checksum_batch", "rx_verify_batch", "device_count", "version", "build_id", "LIB_PATH",
     "CRC32_RESIDUE", "RxRing", "RxFilter", "RX_NO_FCS", "research_lib",
-    "RxPorts", "DELIVERY_DTYPE", "rx_deliver", "rx_deliver_batch", "rx_deliver_ws_bytes",
+    "RxPorts", "DELIVERY_DTYPE", "rx_deliver", "rx_deliver_batch", "rx_deliver_ws_bytes", "rx_verify_deliver_batch",
     "H_ETH", "H_IP4", "H_IP6", "H_TCP", "H_UDP", "H_COUNT", "H_NONE", "DLV_RST", "DLV_IP6", "DLV_FCS",
 ]
 
@@ -174,6 +174,14 @@ _sig = {
     "lnx_rx_deliver_ws_bytes": (ctypes.c_uint64, [ctypes.c_uint64]),
     "lnx_rx_deliver_batch": (ctypes.c_int, [_vp, _vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.POINTER(RxFilter),
                                             ctypes.POINTER(RxPorts), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lnx_rx_verify_deliver_batch": (ctypes.c_int, [_vp, _vp, ctypes.c_uint64, ctypes.c_uint32,
+                                                   ctypes.POINTER(RxFilter), ctypes.POINTER(RxPorts), _vp, _vp, _vp,
+                                                   _vp, _vp, _vp, _vp]),
+    "lnx_rx_ring_set_ports": (ctypes.c_int, [_vp, ctypes.POINTER(RxPorts)]),
+    "lnx_rx_ring_ingress_deliver": (ctypes.c_int, [_vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
+                                                   ctypes.c_uint32, _vp, _vp, _vp, _vp, _vp]),
+    "lnx_ingress_packets_deliver": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
+                                                   _vp, _vp, _vp, _vp, _vp]),
     "lnx_ingress_verdict": (ctypes.c_int, [_vp, ctypes.c_size_t, ctypes.c_uint32, ctypes.POINTER(RxFilter)]),
     "lnx_pcap_checksums": (ctypes.c_int, [_vp, ctypes.c_size_t]),
     "lnx_pcap_verify_batch": (ctypes.c_int, [_vp, _vp, ctypes.c_uint64, _vp, _vp]),
@@ -721,6 +729,41 @@ def rx_deliver_batch(d_bytes, d_off, d_verdict, d_fcs_ok=None, flags: int = 0, f
     return rec, (order[:n] if group else None), count
 
 
+def rx_verify_deliver_batch(d_bytes, d_off, flags: int = 0, filter: RxFilter | None = None,
+                            ports: RxPorts | None = None, group: bool = True, stream=None):
+    """The receive check and the delivery records from ONE read of each frame
+    (lnx_rx_verify_deliver_batch): returns (ok, verdict, rec, order, count) —
+    ok and verdict as rx_verify_batch gives them, rec / order / count as
+    rx_deliver_batch gives them behind it.  flags: VERIFY_EVIL_BIT | VERIFY_ICMP
+    | RX_NO_FCS.  Without ``group`` order and count are None and no workspace is
+    allocated."""
+    import torch
+    what = "lnx_rx_verify_deliver_batch"
+    b = _Batch(what, [("d_bytes", d_bytes, "u8"), ("d_off", d_off, "i64")], stream)
+    n = d_off.numel() - 1
+    if n < 0:
+        raise LnetoError(f"{what}: d_off holds no offset")
+    ok = torch.empty(n, dtype=torch.uint8, device=b.device)
+    verdict = torch.empty(n, dtype=torch.uint8, device=b.device)
+    rec = torch.empty((n, 16), dtype=torch.uint8, device=b.device)
+    order = count = ws = None
+    if group:
+        order = torch.empty(max(n, 1), dtype=torch.int32, device=b.device)  # (n = 0: still a pointer to pass)
+        count = torch.empty(H_COUNT + 1, dtype=torch.int32, device=b.device)
+        ws = torch.empty(rx_deliver_ws_bytes(n), dtype=torch.uint8, device=b.device)
+    with b as s:
+        _check(lib.lnx_rx_verify_deliver_batch(d_bytes.data_ptr(), d_off.data_ptr(), n, flags,
+                                               ctypes.byref(filter) if filter is not None else None,
+                                               ctypes.byref(ports) if ports is not None else None,
+                                               ok.data_ptr(), verdict.data_ptr(), rec.data_ptr(),
+                                               order.data_ptr() if group else None,
+                                               count.data_ptr() if group else None, ws.data_ptr() if group else None, s),
+               what)
+        if ws is not None and stream is not None:
+            ws.record_stream(stream)  # freed on return: not to be reused before the stream is done with it
+    return ok, verdict, rec, (order[:n] if group else None), count
+
+
 PCAP_IP_HDR_BAD, PCAP_PROTO_BAD = 1, 2  # LNX_PCAP_IP_HDR_BAD, LNX_PCAP_PROTO_BAD
 
 
@@ -934,6 +977,54 @@ class RxRing:
         _check(lib.lnx_ingress_packets(self._h, ptrs, lens.ctypes.data, n, offset, flags, ok.ctypes.data,
                                        verdict.ctypes.data), "lnx_ingress_packets")
         return ok[:n], verdict[:n]
+
+    def set_ports(self, ports: RxPorts | None) -> None:
+        """The ring's StackPorts tables for its deliver entries (lnx_rx_ring_set_ports;
+        a copy is kept); None = every port has a handler, the default."""
+        _check(lib.lnx_rx_ring_set_ports(self._h, ctypes.byref(ports) if ports is not None else None),
+               "lnx_rx_ring_set_ports")
+
+    def ingress_deliver(self, first: int = 0, count: int | None = None, offset: int = 0, flags: int = 0,
+                        group: bool = True):
+        """ingress() plus each frame's delivery record from the same read
+        (lnx_rx_ring_ingress_deliver): returns (fcs_ok, verdict, rec, order, count) —
+        rec a DELIVERY_DTYPE array; with ``group`` order (uint32) lists the call's
+        frames by ascending handler id in arrival order and count (H_COUNT + 1) the
+        buckets' sizes, else both are None."""
+        import numpy as np
+        if count is None:
+            count = self.nslots - first
+        ok = np.zeros(max(count, 1), dtype=np.uint8)
+        verdict = np.zeros(max(count, 1), dtype=np.uint8)
+        rec = np.zeros(max(count, 1), dtype=DELIVERY_DTYPE)
+        order = np.zeros(max(count, 1), dtype=np.uint32) if group else None
+        cnt = np.zeros(H_COUNT + 1, dtype=np.uint32) if group else None
+        _check(lib.lnx_rx_ring_ingress_deliver(self._h, first, count, offset, flags, ok.ctypes.data, verdict.ctypes.data,
+                                               rec.ctypes.data, order.ctypes.data if group else None,
+                                               cnt.ctypes.data if group else None), "lnx_rx_ring_ingress_deliver")
+        return ok[:count], verdict[:count], rec[:count], (order[:count] if group else None), cnt
+
+    def ingress_packets_deliver(self, bufs, offset: int = 0, flags: int = 0, group: bool = True):
+        """ingress_packets() plus the delivery records (lnx_ingress_packets_deliver):
+        returns (fcs_ok, verdict, rec, order, count) as ingress_deliver."""
+        import numpy as np
+        if not isinstance(offset, int) or not 0 <= offset < 2**32:
+            raise LnetoError("ingress_packets_deliver: offset must be an int in [0, 2**32)")
+        arrs = [np.frombuffer(bytes(b), dtype=np.uint8) if not isinstance(b, np.ndarray)
+                else np.ascontiguousarray(b, dtype=np.uint8) for b in bufs]
+        n = len(arrs)
+        ptrs = (ctypes.c_void_p * max(n, 1))(*[a.ctypes.data if a.size else None for a in arrs])
+        lens = np.array([a.size for a in arrs] or [0], dtype=np.uint32)
+        ok = np.zeros(max(n, 1), dtype=np.uint8)
+        verdict = np.zeros(max(n, 1), dtype=np.uint8)
+        rec = np.zeros(max(n, 1), dtype=DELIVERY_DTYPE)
+        order = np.zeros(max(n, 1), dtype=np.uint32) if group else None
+        cnt = np.zeros(H_COUNT + 1, dtype=np.uint32) if group else None
+        _check(lib.lnx_ingress_packets_deliver(self._h, ptrs, lens.ctypes.data, n, offset, flags, ok.ctypes.data,
+                                               verdict.ctypes.data, rec.ctypes.data,
+                                               order.ctypes.data if group else None,
+                                               cnt.ctypes.data if group else None), "lnx_ingress_packets_deliver")
+        return ok[:n], verdict[:n], rec[:n], (order[:n] if group else None), cnt
 
     def egress_packets(self, bufs, sizes, offset: int = 0, capacity: int | None = None,
                        flags: int = 3):

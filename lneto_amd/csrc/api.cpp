@@ -622,6 +622,42 @@ int lnx_rx_deliver_batch(const uint8_t* d_bytes, const uint64_t* d_off, uint64_t
   return LNX_OK;
 }
 
+// The receive check and the delivery records from one read of each frame
+// (rx_verify_kernel.hip rv_check with DLV), then the grouping
+// launches on the keys it wrote.  As lnx_rx_deliver_batch it works in the
+// caller's workspace alone.
+int lnx_rx_verify_deliver_batch(const uint8_t* d_bytes, const uint64_t* d_off, uint64_t n, uint32_t flags,
+                                const lnx_rx_filter* filter, const lnx_rx_ports* ports, uint8_t* d_fcs_ok,
+                                uint8_t* d_verdict, lnx_rx_delivery* d_rec, uint32_t* d_order, uint32_t* d_count,
+                                void* d_ws, void* stream) {
+  RxFilter filt;
+  if (!rx_filter_of(filter, &filt)) return LNX_EINVAL;
+  if (flags & ~(uint32_t)(LNX_VERIFY_EVIL_BIT | LNX_VERIFY_ICMP | LNX_RX_NO_FCS)) return LNX_EINVAL;
+  if (ports && (ports->n_tcp > 256u || ports->n_udp > 256u)) return LNX_EINVAL;
+  if ((d_order == nullptr) != (d_count == nullptr)) return LNX_EINVAL;
+  if (n >> 32) return LNX_EINVAL;
+  auto misaligned = [](const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; };
+  if (misaligned(d_rec, 16) || misaligned(d_order, 4) || misaligned(d_count, 4) || misaligned(d_ws, 4)) return LNX_EINVAL;
+  const hipStream_t hs = static_cast<hipStream_t>(stream);
+  if (n == 0) {
+    if (!d_count) return LNX_OK;
+    const hipError_t e = hipMemsetAsync(d_count, 0, (LNX_H_COUNT + 1u) * sizeof(uint32_t), hs);
+    return e == hipSuccess ? LNX_OK : hip_fail(e, "hipMemsetAsync(d_count)");
+  }
+  if (!d_bytes || !d_off || !d_fcs_ok || !d_verdict || !d_rec || (d_order && !d_ws)) return LNX_EINVAL;
+  DeviceCtx* c = nullptr;
+  int st = get_ctx(&c);
+  if (st != LNX_OK) return st;
+  hipError_t e = lnxd::launch_rx_verify_deliver(d_bytes, d_off, n, flags & (LNX_VERIFY_EVIL_BIT | LNX_VERIFY_ICMP),
+                                                !(flags & LNX_RX_NO_FCS), d_fcs_ok, d_verdict, nullptr, &filt, ports,
+                                                d_rec, d_order ? lnxd::deliver_keys(d_ws, n) : nullptr, c->d_rx,
+                                                c->num_cus, hs);
+  if (e != hipSuccess) return hip_fail(e, "rx_verify_deliver_kernel launch");
+  if (d_order && (e = lnxd::launch_deliver_group(n, d_order, d_count, d_ws, hs)) != hipSuccess)
+    return hip_fail(e, "deliver grouping launches");
+  return LNX_OK;
+}
+
 int lnx_pcap_verify_batch(const uint8_t* d_bytes, const uint64_t* d_off, uint64_t n, uint8_t* d_status,
                           void* stream) {
   if (n == 0) return LNX_OK;
@@ -812,7 +848,9 @@ const char* lnx_version(void) {
          "workgroup per frame) + running internet checksums (raw 32-bit sums at either byte phase, frames made of "
          "segments: the sum16 line rows into E / O planes, a 16-lane row or the workgroup's four waves per frame) + "
          "receive delivery (the port stage: a 16-lane row per frame, header bytes only, port tables in LDS; frames "
-         "grouped by handler in arrival order by a counting sort over contiguous slices)";
+         "grouped by handler in arrival order by a counting sort over contiguous slices) + receive check and "
+         "delivery records in one read (the receive kernel's frame lane applies the port stage to its staged "
+         "header; the ring's deliver entries on every route)";
 }
 
 }  // extern "C"

@@ -22,12 +22,6 @@
 
 namespace lnxd {
 
-// the port tables as a kernel argument (on = 0: no tables, every port has a handler)
-struct DlvPorts {
-  uint32_t on, n_tcp, n_udp;
-  uint16_t tcp[kPortsMax], udp[kPortsMax];
-};
-
 constexpr int kRecBlock = 256;                 // 16 rows: 16 frames a pass
 constexpr uint32_t kRecRows = kRecBlock / 16;
 constexpr uint32_t kRecGridCap = 2048;         // workgroups of the records launch (grid-strided past it)
@@ -250,25 +244,20 @@ static uint32_t grp_grid(uint64_t n) {
 }
 uint64_t deliver_ws_bytes(uint64_t n) { return (uint64_t)grp_grid(n) * kBuckets * 4u + 2u * n; }
 
-// ports NULL: no tables.  order / count both NULL: the records alone.
-hipError_t launch_deliver(const uint8_t* bytes, const uint64_t* off, uint64_t n, uint32_t trim, const lnx::RxFilter& filt,
-                          const lnx_rx_ports* ports, const uint8_t* fcs_ok, const uint8_t* verdict, lnx_rx_delivery* rec,
-                          uint32_t* order, uint32_t* count, void* ws, hipStream_t stream) {
+// the keys' place in ws (n: the frames the grouping launches will take)
+uint16_t* deliver_keys(void* ws, uint64_t n) {
+  return reinterpret_cast<uint16_t*>(static_cast<uint32_t*>(ws) + (uint64_t)grp_grid(n) * kBuckets);
+}
+
+// The three grouping launches over keys that launches before them on `stream`
+// wrote at deliver_keys(ws, n): the records launch below, or the receive check
+// that writes records and keys itself (rx_verify_kernel.hip).
+hipError_t launch_deliver_group(uint64_t n, uint32_t* order, uint32_t* count, void* ws, hipStream_t stream) {
   if (n == 0) return hipSuccess;
-  DlvPorts pt{};
-  if (ports) {
-    pt.on = 1, pt.n_tcp = ports->n_tcp, pt.n_udp = ports->n_udp;
-    for (uint32_t i = 0; i < kPortsMax; ++i) pt.tcp[i] = ports->tcp[i], pt.udp[i] = ports->udp[i];
-  }
   const uint32_t G = grp_grid(n);
   uint32_t* hist = static_cast<uint32_t*>(ws);
-  uint16_t* keys = order ? reinterpret_cast<uint16_t*>(hist + (uint64_t)G * kBuckets) : nullptr;
-  uint64_t grid = (n + kRecRows - 1) / kRecRows;
-  if (grid > kRecGridCap) grid = kRecGridCap;
-  hipLaunchKernelGGL(deliver_records_kernel, dim3((unsigned)grid), dim3(kRecBlock), 0, stream, bytes, off, n, trim, filt,
-                     pt, fcs_ok, verdict, reinterpret_cast<uint4*>(rec), keys);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess || !order) return e;
+  const uint16_t* keys = deliver_keys(ws, n);
+  hipError_t e;
   hipLaunchKernelGGL(deliver_hist_kernel, dim3(G), dim3(kGrpBlock), 0, stream, keys, n, hist);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   hipLaunchKernelGGL(deliver_scan_kernel, dim3((kBuckets + 63u) / 64u), dim3(64 * kScanWaves), 0, stream, hist, G,
@@ -276,6 +265,22 @@ hipError_t launch_deliver(const uint8_t* bytes, const uint64_t* off, uint64_t n,
   if ((e = hipGetLastError()) != hipSuccess) return e;
   hipLaunchKernelGGL(deliver_scatter_kernel, dim3(G), dim3(kGrpBlock), 0, stream, keys, n, hist, count, order);
   return hipGetLastError();
+}
+
+// ports NULL: no tables.  order / count both NULL: the records alone.
+hipError_t launch_deliver(const uint8_t* bytes, const uint64_t* off, uint64_t n, uint32_t trim, const lnx::RxFilter& filt,
+                          const lnx_rx_ports* ports, const uint8_t* fcs_ok, const uint8_t* verdict, lnx_rx_delivery* rec,
+                          uint32_t* order, uint32_t* count, void* ws, hipStream_t stream) {
+  if (n == 0) return hipSuccess;
+  const DlvPorts pt = dlv_ports_of(ports);
+  uint16_t* keys = order ? deliver_keys(ws, n) : nullptr;
+  uint64_t grid = (n + kRecRows - 1) / kRecRows;
+  if (grid > kRecGridCap) grid = kRecGridCap;
+  hipLaunchKernelGGL(deliver_records_kernel, dim3((unsigned)grid), dim3(kRecBlock), 0, stream, bytes, off, n, trim, filt,
+                     pt, fcs_ok, verdict, reinterpret_cast<uint4*>(rec), keys);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess || !order) return e;
+  return launch_deliver_group(n, order, count, ws, stream);
 }
 
 }  // namespace lnxd

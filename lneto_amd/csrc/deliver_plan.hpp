@@ -59,6 +59,21 @@ constexpr uint32_t kDlvRst = LNX_DLV_RST, kDlvIp6 = LNX_DLV_IP6, kDlvFcs = LNX_D
 constexpr uint32_t kDropped = 2, kBadCRC = 3, kShortBuffer = 6, kTruncated = 18;
 constexpr uint32_t kPortsMax = 256;
 
+// the port tables as a kernel argument (on = 0: no tables, every port has a handler)
+struct DlvPorts {
+  uint32_t on, n_tcp, n_udp;
+  uint16_t tcp[kPortsMax], udp[kPortsMax];
+};
+// ports NULL: no tables
+inline DlvPorts dlv_ports_of(const lnx_rx_ports* ports) {
+  DlvPorts pt{};
+  if (ports) {
+    pt.on = 1, pt.n_tcp = ports->n_tcp, pt.n_udp = ports->n_udp;
+    for (uint32_t i = 0; i < kPortsMax; ++i) pt.tcp[i] = ports->tcp[i], pt.udp[i] = ports->udp[i];
+  }
+  return pt;
+}
+
 struct DlvPlan {
   uint32_t ip_end = 0, handler = kHNone, l4_off = 0, src_port = 0, dst_port = 0, verdict = 0, flags = 0;
   uint32_t lookup = 0;  // 6 / 17: dst_port is to be looked up in the TCP / UDP table (dlv_finish); 0: decided

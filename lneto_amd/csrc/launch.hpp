@@ -36,6 +36,14 @@ uint64_t deliver_ws_bytes(uint64_t n);
 hipError_t launch_deliver(const uint8_t* bytes, const uint64_t* off, uint64_t n, uint32_t trim, const lnx::RxFilter& filt,
                           const lnx_rx_ports* ports, const uint8_t* fcs_ok, const uint8_t* verdict, lnx_rx_delivery* rec,
                           uint32_t* order, uint32_t* count, void* ws, hipStream_t stream);
+uint16_t* deliver_keys(void* ws, uint64_t n);
+hipError_t launch_deliver_group(uint64_t n, uint32_t* order, uint32_t* count, void* ws, hipStream_t stream);
+// rx_verify_kernel.hip: the receive check that writes the delivery records too
+hipError_t launch_rx_verify_deliver(const uint8_t* bytes, const uint64_t* off, uint64_t n, uint32_t flags, bool fcs,
+                                    uint8_t* ok, uint8_t* verdict, const uint32_t* seg_len,
+                                    const lnx::RxFilter* filter, const lnx_rx_ports* ports, lnx_rx_delivery* rec,
+                                    uint16_t* keys, const uint32_t* image, int num_cus, hipStream_t stream,
+                                    bool host = false);
 }  // namespace lnxd
 
 namespace lnx {

@@ -41,6 +41,13 @@
 // Stack configuration (lnx_rx_ring_set_filter) and FCS-less devices
 // (LNX_RX_NO_FCS) follow the reference's receive path exactly
 // (ingress_kernel.hip, rx_filter.hpp).
+//
+// Delivery: lnx_rx_ring_ingress_deliver and
+// lnx_ingress_packets_deliver take the same routes with the receive check that
+// also writes each frame's delivery record (rx_verify_deliver_kernel: the
+// header lines cross PCIe once), group every internal batch by handler in its
+// stage's pipeline, and merge the batches' groups into the call's on the host
+// (deliver_group.hpp).  Their buffers exist from the first such call on.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstdint>
@@ -49,6 +56,7 @@
 #include <thread>
 #include <vector>
 #include "../../include/lneto_amd.h"
+#include "deliver_group.hpp"
 #include "host_path.hpp"
 #include "launch.hpp"
 #include "rx_filter.hpp"
@@ -93,9 +101,27 @@ struct lnx_rx_ring {
     uint32_t* h_len = nullptr;
     uint8_t* h_ok = nullptr;
     uint8_t* h_verdict = nullptr;
+    // the deliver entries' (ensure_deliver): a batch's records, its order and
+    // bucket sizes, the grouping launches' workspace, and pinned copies
+    lnx_rx_delivery* d_rec = nullptr;
+    uint32_t* d_order = nullptr;
+    uint32_t* d_count = nullptr;
+    void* d_ws = nullptr;
+    lnx_rx_delivery* h_rec = nullptr;
+    uint32_t* h_order = nullptr;
+    uint32_t* h_count = nullptr;
   };
   std::vector<Stage> st;
   RxFilter filt{};  // lnx_rx_ring_set_filter; on = 0: accept-all
+  lnx_rx_filter cfilt{};  // the same as the caller gave it (the host path's lnx_rx_deliver)
+  bool has_filt = false;
+  lnx_rx_ports ports{};  // lnx_rx_ring_set_ports
+  bool has_ports = false;  // false: every port has a handler
+  // per slot / per internal batch of lnx_rx_ring_ingress_deliver (pinned; ensure_deliver)
+  bool deliver_ready = false;
+  lnx_rx_delivery* h_rec = nullptr;
+  uint32_t* h_order = nullptr;
+  uint32_t* h_count = nullptr;
   // batches of fewer frames run on the host (host_path.cpp), no launch
   // (lnx_rx_ring_set_host_threshold; the default is the measured crossover)
   uint32_t host_below = LNX_HOST_BATCH_DEFAULT;
@@ -126,8 +152,18 @@ void ring_free(lnx_rx_ring* r) {
     (void)hipHostFree(s.h_len);
     (void)hipHostFree(s.h_ok);
     (void)hipHostFree(s.h_verdict);
+    (void)hipFree(s.d_rec);
+    (void)hipFree(s.d_order);
+    (void)hipFree(s.d_count);
+    (void)hipFree(s.d_ws);
+    (void)hipHostFree(s.h_rec);
+    (void)hipHostFree(s.h_order);
+    (void)hipHostFree(s.h_count);
     if (s.s) (void)hipStreamDestroy(s.s);
   }
+  (void)hipHostFree(r->h_rec);
+  (void)hipHostFree(r->h_order);
+  (void)hipHostFree(r->h_count);
   (void)hipHostFree(r->h_slots);
   (void)hipHostFree(r->h_len);
   (void)hipHostFree(r->h_ok);
@@ -198,18 +234,36 @@ bool in_ring(const lnx_rx_ring* r, const uint8_t* b, uint64_t offset, uint64_t n
 // Receive direction on stage s (asynchronous), results into ok_dst /
 // verdict_dst (pinned, nb entries), frames as `src` says.  FCS verify unless
 // LNX_RX_NO_FCS (then fcs_ok = 1 and the verdict covers the whole frame).
+// dv (the deliver entries): the check that also writes the batch's records,
+// then the grouping launches when dv->order_dst is given, results into
+// dv's pinned destinations (nb records, nb order entries, kGroupBuckets counts).
+struct DlvDst {
+  lnx_rx_delivery* rec_dst;
+  uint32_t* order_dst;
+  uint32_t* count_dst;
+};
 int enqueue_rx(lnx_rx_ring* r, Stage& s, uint32_t nb, RxSrc src, uint32_t b0, uint32_t offset, uint32_t flags,
-               uint8_t* ok_dst, uint8_t* verdict_dst) {
+               uint8_t* ok_dst, uint8_t* verdict_dst, const DlvDst* dv = nullptr) {
   hipError_t e;
   const bool fcs = !(flags & LNX_RX_NO_FCS);
   const uint32_t vflags = flags & (LNX_VERIFY_EVIL_BIT | LNX_VERIFY_ICMP);
   const uint32_t* rx_image = static_cast<const uint32_t*>(r->rx_image);
+  const bool group = dv && dv->order_dst;
+  auto verify = [&](const uint8_t* bytes, const uint64_t* off, uint64_t n, uint32_t vf, bool with_fcs,
+                              uint8_t* ok, uint8_t* verdict, const uint32_t* seg_len, const RxFilter* filter,
+                              const uint32_t* image, int num_cus, hipStream_t stream, bool host = false) {
+    if (!dv)
+      return launch_rx_verify(bytes, off, n, vf, with_fcs, ok, verdict, seg_len, filter, image, num_cus, stream, host);
+    return lnxd::launch_rx_verify_deliver(bytes, off, n, vf, with_fcs, ok, verdict, seg_len, filter,
+                                          r->has_ports ? &r->ports : nullptr, s.d_rec,
+                                          group ? lnxd::deliver_keys(s.d_ws, n) : nullptr, image, num_cus, stream, host);
+  };
   if (src == RxSrc::kSegDirect) {
     if ((e = hipMemcpyAsync(s.d_start, s.h_off, (size_t)nb * 8, hipMemcpyHostToDevice, s.s)) != hipSuccess ||
         (e = hipMemcpyAsync(s.d_len, s.h_len, (size_t)nb * 4, hipMemcpyHostToDevice, s.s)) != hipSuccess)
       return hip_error(e, "rx ring H2D (frame table)");
-    if ((e = launch_rx_verify(r->d_slots, s.d_start, nb, vflags, fcs, s.d_ok, s.d_verdict, s.d_len, &r->filt,
-                              rx_image, r->num_cus, s.s, true)) != hipSuccess)
+    if ((e = verify(r->d_slots, s.d_start, nb, vflags, fcs, s.d_ok, s.d_verdict, s.d_len, &r->filt, rx_image,
+                    r->num_cus, s.s, true)) != hipSuccess)
       return hip_error(e, "rx ring rx_verify launch");
   } else if (src == RxSrc::kSlotsDirect) {
     if ((e = hipMemcpyAsync(s.d_len, r->h_len + b0, (size_t)nb * 4, hipMemcpyHostToDevice, s.s)) != hipSuccess)
@@ -217,8 +271,8 @@ int enqueue_rx(lnx_rx_ring* r, Stage& s, uint32_t nb, RxSrc src, uint32_t b0, ui
     const uint32_t grid = std::min<uint32_t>((nb + 255) / 256, 1024);
     hipLaunchKernelGGL(ring_segments_kernel, dim3(grid), dim3(256), 0, s.s, s.d_start, s.d_len, nb, r->cap, offset);
     if ((e = hipGetLastError()) != hipSuccess) return hip_error(e, "ring_segments_kernel launch");
-    if ((e = launch_rx_verify(r->d_slots + (size_t)b0 * r->cap, s.d_start, nb, vflags, fcs, s.d_ok, s.d_verdict,
-                              s.d_len, &r->filt, rx_image, r->num_cus, s.s, true)) != hipSuccess)
+    if ((e = verify(r->d_slots + (size_t)b0 * r->cap, s.d_start, nb, vflags, fcs, s.d_ok, s.d_verdict, s.d_len,
+                    &r->filt, rx_image, r->num_cus, s.s, true)) != hipSuccess)
       return hip_error(e, "rx ring rx_verify launch");
   } else if (src == RxSrc::kPacked) {
     const uint64_t total = s.h_off[nb];
@@ -226,8 +280,8 @@ int enqueue_rx(lnx_rx_ring* r, Stage& s, uint32_t nb, RxSrc src, uint32_t b0, ui
         (e = hipMemcpyAsync(s.d_start, s.h_off, (size_t)(nb + 1) * 8, hipMemcpyHostToDevice, s.s)) != hipSuccess)
       return hip_error(e, "rx ring H2D (packed)");
     // FCS and verdicts in one pass over each frame (rx_verify_kernel.hip)
-    if ((e = launch_rx_verify(s.d_bytes, s.d_start, nb, vflags, fcs, s.d_ok, s.d_verdict, nullptr, &r->filt,
-                              rx_image, r->num_cus, s.s)) != hipSuccess)
+    if ((e = verify(s.d_bytes, s.d_start, nb, vflags, fcs, s.d_ok, s.d_verdict, nullptr, &r->filt, rx_image,
+                    r->num_cus, s.s)) != hipSuccess)
       return hip_error(e, "rx ring rx_verify launch");
   } else {
     const size_t cap = r->cap;
@@ -238,13 +292,24 @@ int enqueue_rx(lnx_rx_ring* r, Stage& s, uint32_t nb, RxSrc src, uint32_t b0, ui
     const uint32_t grid = std::min<uint32_t>((nb + 255) / 256, 1024);
     hipLaunchKernelGGL(ring_segments_kernel, dim3(grid), dim3(256), 0, s.s, s.d_start, s.d_len, nb, r->cap, offset);
     if ((e = hipGetLastError()) != hipSuccess) return hip_error(e, "ring_segments_kernel launch");
-    if ((e = launch_rx_verify(s.d_bytes, s.d_start, nb, vflags, fcs, s.d_ok, s.d_verdict, s.d_len, &r->filt,
-                              rx_image, r->num_cus, s.s)) != hipSuccess)
+    if ((e = verify(s.d_bytes, s.d_start, nb, vflags, fcs, s.d_ok, s.d_verdict, s.d_len, &r->filt, rx_image,
+                    r->num_cus, s.s)) != hipSuccess)
       return hip_error(e, "rx ring rx_verify launch");
   }
   if ((e = hipMemcpyAsync(ok_dst, s.d_ok, nb, hipMemcpyDeviceToHost, s.s)) != hipSuccess ||
       (e = hipMemcpyAsync(verdict_dst, s.d_verdict, nb, hipMemcpyDeviceToHost, s.s)) != hipSuccess)
     return hip_error(e, "rx ring D2H");
+  if (dv) {
+    if (group && (e = lnxd::launch_deliver_group(nb, s.d_order, s.d_count, s.d_ws, s.s)) != hipSuccess)
+      return hip_error(e, "rx ring deliver grouping launches");
+    if ((e = hipMemcpyAsync(dv->rec_dst, s.d_rec, (size_t)nb * sizeof(lnx_rx_delivery), hipMemcpyDeviceToHost, s.s)) !=
+            hipSuccess ||
+        (group && ((e = hipMemcpyAsync(dv->order_dst, s.d_order, (size_t)nb * 4, hipMemcpyDeviceToHost, s.s)) !=
+                       hipSuccess ||
+                   (e = hipMemcpyAsync(dv->count_dst, s.d_count, (size_t)lnxd::kGroupBuckets * 4, hipMemcpyDeviceToHost,
+                                       s.s)) != hipSuccess)))
+      return hip_error(e, "rx ring D2H (delivery)");
+  }
   r->stats.device_batches += 1;
   r->stats.device_frames += nb;
   return LNX_OK;
@@ -302,6 +367,74 @@ void host_rx(const lnx_rx_ring* r, const uint8_t* p, uint32_t len, uint32_t flag
   *ok = fcs ? host_fcs_ok(p, len) : 1u;
   *verdict = host_verdict(p, len > trim ? len - trim : 0u, flags & (LNX_VERIFY_EVIL_BIT | LNX_VERIFY_ICMP), r->filt);
 }
+
+// The caller's delivery outputs of one call (the deliver entries): rec is
+// required, order / count both given or both NULL.
+struct DlvOut {
+  lnx_rx_delivery* rec;
+  uint32_t* order;
+  uint32_t* count;
+};
+
+// host_rx, then the frame's delivery record (lnx_rx_deliver with the ring's filter and ports)
+void host_rx_deliver(const lnx_rx_ring* r, const uint8_t* p, uint32_t len, uint32_t flags, uint8_t* ok, uint8_t* verdict,
+                     lnx_rx_delivery* rec) {
+  host_rx(r, p, len, flags, ok, verdict);
+  const bool fcs = !(flags & LNX_RX_NO_FCS);
+  const uint32_t trim = fcs ? 4u : 0u;
+  (void)lnx_rx_deliver(p, len > trim ? len - trim : 0u, r->has_filt ? &r->cfilt : nullptr,
+                       r->has_ports ? &r->ports : nullptr, fcs ? (int)*ok : -1, *verdict, rec);
+}
+
+// The deliver entries' buffers, made by the first call that needs them: per
+// stage a batch's records, order, bucket sizes and grouping workspace on the
+// device with pinned copies, and per slot / per internal batch the pinned
+// results of lnx_rx_ring_ingress_deliver.  The other entries never come here.
+int ensure_deliver(lnx_rx_ring* r) {
+  if (r->deliver_ready) return LNX_OK;
+  hipError_t e = hipSetDevice(r->device);
+  if (e != hipSuccess) return hip_error(e, "hipSetDevice");
+  const size_t nb = r->batch, nbatches = ((size_t)r->nslots + r->batch - 1) / r->batch;
+  const size_t cb = (size_t)lnxd::kGroupBuckets * 4;
+  auto fail = [&](const char* what) {
+    const int rc = hip_error(e, what);
+    for (auto& s : r->st) {
+      (void)hipFree(s.d_rec), (void)hipFree(s.d_order), (void)hipFree(s.d_count), (void)hipFree(s.d_ws);
+      (void)hipHostFree(s.h_rec), (void)hipHostFree(s.h_order), (void)hipHostFree(s.h_count);
+      s.d_rec = nullptr, s.d_order = nullptr, s.d_count = nullptr, s.d_ws = nullptr;
+      s.h_rec = nullptr, s.h_order = nullptr, s.h_count = nullptr;
+    }
+    (void)hipHostFree(r->h_rec), (void)hipHostFree(r->h_order), (void)hipHostFree(r->h_count);
+    r->h_rec = nullptr, r->h_order = nullptr, r->h_count = nullptr;
+    return rc;
+  };
+  for (auto& s : r->st) {
+    if ((e = hipMalloc(reinterpret_cast<void**>(&s.d_rec), nb * sizeof(lnx_rx_delivery))) != hipSuccess ||
+        (e = hipMalloc(reinterpret_cast<void**>(&s.d_order), nb * 4)) != hipSuccess ||
+        (e = hipMalloc(reinterpret_cast<void**>(&s.d_count), cb)) != hipSuccess ||
+        (e = hipMalloc(&s.d_ws, lnxd::deliver_ws_bytes(nb))) != hipSuccess ||
+        (e = hipHostMalloc(reinterpret_cast<void**>(&s.h_rec), nb * sizeof(lnx_rx_delivery), hipHostMallocDefault)) !=
+            hipSuccess ||
+        (e = hipHostMalloc(reinterpret_cast<void**>(&s.h_order), nb * 4, hipHostMallocDefault)) != hipSuccess ||
+        (e = hipHostMalloc(reinterpret_cast<void**>(&s.h_count), cb, hipHostMallocDefault)) != hipSuccess)
+      return fail("rx ring deliver stage allocation");
+  }
+  if ((e = hipHostMalloc(reinterpret_cast<void**>(&r->h_rec), (size_t)r->nslots * sizeof(lnx_rx_delivery),
+                         hipHostMallocDefault)) != hipSuccess ||
+      (e = hipHostMalloc(reinterpret_cast<void**>(&r->h_order), (size_t)r->nslots * 4, hipHostMallocDefault)) !=
+          hipSuccess ||
+      (e = hipHostMalloc(reinterpret_cast<void**>(&r->h_count), nbatches * cb, hipHostMallocDefault)) != hipSuccess)
+    return fail("rx ring deliver allocation");
+  r->deliver_ready = true;
+  return LNX_OK;
+}
+
+// lnx_rx_ring_ingress (dv NULL) and lnx_rx_ring_ingress_deliver
+int ring_ingress(lnx_rx_ring* r, uint32_t first, uint32_t count, uint32_t offset, uint32_t flags, uint8_t* fcs_ok,
+                 uint8_t* verdict, const DlvOut* dv);
+// lnx_ingress_packets (dv NULL) and lnx_ingress_packets_deliver
+int ingress_packets(lnx_rx_ring* r, const uint8_t* const* bufs, const uint32_t* lens, uint64_t n, uint32_t offset,
+                    uint32_t flags, uint8_t* fcs_ok, uint8_t* verdict, const DlvOut* dv);
 
 }  // namespace
 
@@ -395,29 +528,86 @@ int lnx_rx_ring_set_filter(lnx_rx_ring* r, const lnx_rx_filter* filter) {
   if (!rx_filter_of(filter, &f)) return LNX_EINVAL;
   std::lock_guard<std::mutex> lk(r->mu);
   r->filt = f;
+  r->has_filt = filter != nullptr;
+  if (filter) r->cfilt = *filter;
   return LNX_OK;
+}
+
+int lnx_rx_ring_set_ports(lnx_rx_ring* r, const lnx_rx_ports* ports) {
+  if (!r || (ports && (ports->n_tcp > 256u || ports->n_udp > 256u))) return LNX_EINVAL;
+  std::lock_guard<std::mutex> lk(r->mu);
+  r->has_ports = ports != nullptr;
+  if (ports) r->ports = *ports;
+  return ensure_deliver(r);
 }
 
 int lnx_rx_ring_ingress(lnx_rx_ring* r, uint32_t first, uint32_t count, uint32_t offset, uint32_t flags,
                         uint8_t* fcs_ok, uint8_t* verdict) {
+  return ring_ingress(r, first, count, offset, flags, fcs_ok, verdict, nullptr);
+}
+
+int lnx_rx_ring_ingress_deliver(lnx_rx_ring* r, uint32_t first, uint32_t count, uint32_t offset, uint32_t flags,
+                                uint8_t* fcs_ok, uint8_t* verdict, lnx_rx_delivery* rec, uint32_t* order,
+                                uint32_t* count_out) {
+  if (!rec || (order == nullptr) != (count_out == nullptr)) return LNX_EINVAL;
+  const DlvOut dv{rec, order, count_out};
+  return ring_ingress(r, first, count, offset, flags, fcs_ok, verdict, &dv);
+}
+
+int lnx_ingress_packets(lnx_rx_ring* r, const uint8_t* const* bufs, const uint32_t* lens, uint64_t n,
+                        uint32_t offset, uint32_t flags, uint8_t* fcs_ok, uint8_t* verdict) {
+  return ingress_packets(r, bufs, lens, n, offset, flags, fcs_ok, verdict, nullptr);
+}
+
+int lnx_ingress_packets_deliver(lnx_rx_ring* r, const uint8_t* const* bufs, const uint32_t* lens, uint64_t n,
+                                uint32_t offset, uint32_t flags, uint8_t* fcs_ok, uint8_t* verdict,
+                                lnx_rx_delivery* rec, uint32_t* order, uint32_t* count_out) {
+  if (!rec || (order == nullptr) != (count_out == nullptr)) return LNX_EINVAL;
+  if (n >> 32) return LNX_EINVAL;  // (order's frame indices are 32-bit)
+  const DlvOut dv{rec, order, count_out};
+  return ingress_packets(r, bufs, lens, n, offset, flags, fcs_ok, verdict, &dv);
+}
+
+}  // extern "C"
+
+namespace {
+
+int ring_ingress(lnx_rx_ring* r, uint32_t first, uint32_t count, uint32_t offset, uint32_t flags, uint8_t* fcs_ok,
+                 uint8_t* verdict, const DlvOut* dv) {
   if (!r) return LNX_EINVAL;
   if ((uint64_t)first + count > r->nslots || offset >= r->cap) return LNX_EINVAL;
-  if (count == 0) return LNX_OK;
+  if (count == 0) {
+    if (dv && dv->count) std::memset(dv->count, 0, (size_t)lnxd::kGroupBuckets * 4);
+    return LNX_OK;
+  }
   std::lock_guard<std::mutex> lk(r->mu);
   if (count < r->host_below) {  // below the crossover: no launch
     for (uint32_t i = first; i < first + count; ++i) {
       const uint32_t l = std::min(r->h_len[i], r->cap);
+      const uint8_t* p = r->h_slots + (size_t)i * r->cap + offset;
       uint8_t ok, v;
-      host_rx(r, r->h_slots + (size_t)i * r->cap + offset, l > offset ? l - offset : 0u, flags, &ok, &v);
+      if (dv) host_rx_deliver(r, p, l > offset ? l - offset : 0u, flags, &ok, &v, dv->rec + (i - first));
+      else host_rx(r, p, l > offset ? l - offset : 0u, flags, &ok, &v);
       if (fcs_ok) fcs_ok[i - first] = ok;
       if (verdict) verdict[i - first] = v;
     }
+    if (dv && dv->order) lnxd::group_records(dv->rec, count, dv->order, dv->count);
     r->stats.host_frames += count;
     return LNX_OK;
   }
   hipError_t e = hipSetDevice(r->device);
   if (e != hipSuccess) return hip_error(e, "hipSetDevice");
-  int rc = LNX_OK;
+  int rc = dv ? ensure_deliver(r) : LNX_OK;
+  if (rc != LNX_OK) return rc;
+  // deliver: batch k's records and order go to the slots' pinned arrays at its
+  // first slot, its bucket sizes to the k-th block of h_count
+  std::vector<uint32_t> bfirst, bn;
+  auto dst = [&](uint32_t b0, uint32_t nb) {
+    const size_t kb = bfirst.size();
+    bfirst.push_back(b0 - first), bn.push_back(nb);
+    return DlvDst{r->h_rec + b0, dv->order ? r->h_order + b0 : nullptr,
+                  dv->order ? r->h_count + kb * lnxd::kGroupBuckets : nullptr};
+  };
   // stage k's staging (h_pack / h_off) was packed and handed to async copies
   // on its stream, and that stream has not been synchronized since: a batch
   // in between that does not use the staging (whole slots) leaves it busy
@@ -437,8 +627,11 @@ int lnx_rx_ring_ingress(lnx_rx_ring* r, uint32_t first, uint32_t count, uint32_t
     // at 1500 B); else, with zero copy, the frames are read in place (only
     // their bytes cross PCIe), without it packed on the host
     const bool dense = total * 10 >= (uint64_t)nb * r->cap * 9;
+    DlvDst dd{};
+    if (dv) dd = dst(b0, nb);
     if (r->zero_copy && !dense) {
-      rc = enqueue_rx(r, s, nb, RxSrc::kSlotsDirect, b0, offset, flags, r->h_ok + b0, r->h_verdict + b0);
+      rc = enqueue_rx(r, s, nb, RxSrc::kSlotsDirect, b0, offset, flags, r->h_ok + b0, r->h_verdict + b0,
+                      dv ? &dd : nullptr);
       if (rc == LNX_OK) r->stats.zero_copy_frames += nb;
       continue;
     }
@@ -452,7 +645,7 @@ int lnx_rx_ring_ingress(lnx_rx_ring* r, uint32_t first, uint32_t count, uint32_t
       packed_pending[k % r->depth] = true;
     }
     rc = enqueue_rx(r, s, nb, pack ? RxSrc::kPacked : RxSrc::kSlotsCopy, b0, offset, flags, r->h_ok + b0,
-                    r->h_verdict + b0);
+                    r->h_verdict + b0, dv ? &dd : nullptr);
   }
   for (auto& s : r->st) {
     const hipError_t se = hipStreamSynchronize(s.s);
@@ -461,30 +654,50 @@ int lnx_rx_ring_ingress(lnx_rx_ring* r, uint32_t first, uint32_t count, uint32_t
   if (rc == LNX_OK) {
     if (fcs_ok) std::memcpy(fcs_ok, r->h_ok + first, count);
     if (verdict) std::memcpy(verdict, r->h_verdict + first, count);
+    if (dv) {
+      std::memcpy(dv->rec, r->h_rec + first, (size_t)count * sizeof(lnx_rx_delivery));
+      if (dv->order)
+        lnxd::merge_groups(r->h_order + first, r->h_count, bfirst.data(), bn.data(), (uint32_t)bn.size(), dv->order,
+                           dv->count);
+    }
   }
   return rc;
 }
 
-int lnx_ingress_packets(lnx_rx_ring* r, const uint8_t* const* bufs, const uint32_t* lens, uint64_t n,
-                        uint32_t offset, uint32_t flags, uint8_t* fcs_ok, uint8_t* verdict) {
+int ingress_packets(lnx_rx_ring* r, const uint8_t* const* bufs, const uint32_t* lens, uint64_t n, uint32_t offset,
+                    uint32_t flags, uint8_t* fcs_ok, uint8_t* verdict, const DlvOut* dv) {
   if (!r || (n > 0 && (!bufs || !lens))) return LNX_EINVAL;
   if (offset >= r->cap) return LNX_EINVAL;
   for (uint64_t i = 0; i < n; ++i)
     if (lens[i] > r->cap || (lens[i] > 0 && !bufs[i])) return LNX_EINVAL;
-  if (n == 0) return LNX_OK;
+  if (n == 0) {
+    if (dv && dv->count) std::memset(dv->count, 0, (size_t)lnxd::kGroupBuckets * 4);
+    return LNX_OK;
+  }
   std::lock_guard<std::mutex> lk(r->mu);
   if (n < r->host_below) {  // below the crossover: no launch (netdev's Runner hands over one buffer per call)
     for (uint64_t i = 0; i < n; ++i) {
       uint8_t ok, v;
-      host_rx(r, bufs[i] + offset, lens[i] > offset ? lens[i] - offset : 0u, flags, &ok, &v);
+      const uint32_t l = lens[i] > offset ? lens[i] - offset : 0u;
+      if (dv) host_rx_deliver(r, bufs[i] + offset, l, flags, &ok, &v, dv->rec + i);
+      else host_rx(r, bufs[i] + offset, l, flags, &ok, &v);
       if (fcs_ok) fcs_ok[i] = ok;
       if (verdict) verdict[i] = v;
     }
+    if (dv && dv->order) lnxd::group_records(dv->rec, n, dv->order, dv->count);
     r->stats.host_frames += n;
     return LNX_OK;
   }
   hipError_t e = hipSetDevice(r->device);
   if (e != hipSuccess) return hip_error(e, "hipSetDevice");
+  if (dv) {
+    const int drc = ensure_deliver(r);
+    if (drc != LNX_OK) return drc;
+  }
+  // deliver: the batches' orders (batch-local indices, at the batch's first
+  // frame) and bucket sizes, kept until the merge at the end of the call
+  const bool group = dv && dv->order;
+  std::vector<uint32_t> all_order(group ? n : 0), all_count, bfirst, bn;
   // Batches go round-robin over the stages; batch k is packed into the
   // staging of stage k % depth after that stage's previous batch has drained,
   // so the gather (host memcpy, parallel) of batch k+1 overlaps the copies
@@ -500,6 +713,12 @@ int lnx_ingress_packets(lnx_rx_ring* r, const uint8_t* const* bufs, const uint32
     if (se != hipSuccess) return hip_error(se, "rx ring hipStreamSynchronize");
     if (fcs_ok) std::memcpy(fcs_ok + f0, r->st[k].h_ok, cnt);
     if (verdict) std::memcpy(verdict + f0, r->st[k].h_verdict, cnt);
+    if (dv) std::memcpy(dv->rec + f0, r->st[k].h_rec, (size_t)cnt * sizeof(lnx_rx_delivery));
+    if (group) {  // (the stages drain in the batches' order: round-robin, one batch a stage)
+      std::memcpy(all_order.data() + f0, r->st[k].h_order, (size_t)cnt * 4);
+      all_count.insert(all_count.end(), r->st[k].h_count, r->st[k].h_count + lnxd::kGroupBuckets);
+      bfirst.push_back((uint32_t)f0), bn.push_back(cnt);
+    }
     return LNX_OK;
   };
   uint64_t i0 = 0;
@@ -509,6 +728,7 @@ int lnx_ingress_packets(lnx_rx_ring* r, const uint8_t* const* bufs, const uint32
     if (rc != LNX_OK) break;
     const uint32_t nb = (uint32_t)std::min<uint64_t>(per, n - i0);
     auto& s = r->st[sk];
+    const DlvDst dd{s.h_rec, group ? s.h_order : nullptr, group ? s.h_count : nullptr};
     auto flen = [&](uint32_t j) -> uint32_t { return lens[i0 + j] > offset ? lens[i0 + j] - offset : 0u; };
     // the caller's buffers are the ring's own slots (RunnerConfig.Buffers from
     // lnx_rx_ring_slots): a frame table only, the kernel reads them in place
@@ -520,18 +740,30 @@ int lnx_ingress_packets(lnx_rx_ring* r, const uint8_t* const* bufs, const uint32
       s.h_len[j] = flen(j);
     }
     if (!direct) pack_batch(s, nb, [&](uint32_t j) { return bufs[i0 + j] + offset; }, flen);
-    rc = enqueue_rx(r, s, nb, direct ? RxSrc::kSegDirect : RxSrc::kPacked, 0, 0, flags, s.h_ok, s.h_verdict);
+    rc = enqueue_rx(r, s, nb, direct ? RxSrc::kSegDirect : RxSrc::kPacked, 0, 0, flags, s.h_ok, s.h_verdict,
+                    dv ? &dd : nullptr);
     if (rc == LNX_OK && direct) r->stats.zero_copy_frames += nb;
     if (rc == LNX_OK) pending[sk] = {i0, nb};
   }
-  for (uint32_t k = 0; k < depth; ++k) {
-    if (!pending[k].second) continue;
+  // (the stages still pending, oldest batch first: the merge takes the batches in arrival order)
+  for (uint32_t j = 0; j < depth; ++j) {
+    uint32_t k = depth;
+    for (uint32_t c = 0; c < depth; ++c)
+      if (pending[c].second && (k == depth || pending[c].first < pending[k].first)) k = c;
+    if (k == depth) break;
     const int d = drain(k);
     if (rc == LNX_OK) rc = d;
   }
+  if (rc == LNX_OK && group)
+    lnxd::merge_groups(all_order.data(), all_count.data(), bfirst.data(), bn.data(), (uint32_t)bn.size(), dv->order,
+                       dv->count);
   if (rc != LNX_OK) quiesce(r);
   return rc;
 }
+
+}  // namespace
+
+extern "C" {
 
 int lnx_egress_packets(lnx_rx_ring* r, uint8_t* const* bufs, uint32_t* lens, uint64_t n, uint32_t offset,
                        uint32_t capacity, uint32_t flags, uint8_t* status) {

@@ -23,6 +23,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <type_traits>
+#include "deliver_plan.hpp"
 #include "frame_plan.hpp"
 #include "launch.hpp"
 #include "rx_filter.hpp"
@@ -596,19 +597,41 @@ __device__ __forceinline__ uint32_t rv_rows(const char* lds, uint2* res, uint2* 
     return rank;
 }
 
-template <bool CRC, bool FILT, bool HOST>
-__global__ void __launch_bounds__(kRvBlock)
-rx_verify_kernel(const uint8_t* __restrict__ bytes, const uint64_t* __restrict__ off, uint64_t n, uint32_t flags,
-                 uint8_t* __restrict__ okv, uint8_t* __restrict__ verdict, const uint32_t* __restrict__ seg_len,
-                 const uint32_t* __restrict__ image, uint32_t gsz, RxFilter filt, const uint32_t* __restrict__ gate,
-                 uint32_t epoch) {
+// The body of lnx::rx_verify_kernel (DLV = false: ports, rec, keys unused) and
+// of lnxd::rx_verify_deliver_kernel (DLV = true), which adds
+// to phase B, by the lane that holds the frame and has its ok and verdict: the
+// frame's lnx_rx_delivery record (deliver_plan.hpp with fcs = ok, or -1 when
+// no CRC is taken, and v_in = the verdict) into rec[f], and its bucket key
+// into keys[f] when keys is not null.  The rules' fields come from the staged
+// head bytes; past them (IPv4 options: the ports and TCP flags at up to offset
+// 86 + 2) from the aligned dword of the frame's own qword that holds the byte,
+// as dyn16 reads.  The port tables sit in LDS behind the waves' staging, 1 KiB:
+// 154 KiB + 1 KiB = 155 KiB of the 160 (158720 bytes) with the CRC tables.
+constexpr uint32_t kDlvTabBytes = 2u * 2u * lnxd::kPortsMax;  // tcp, then udp
+// the workgroup's LDS, declared by the kernel: the CRC tables, the waves' group staging, the port tables
+constexpr uint32_t rv_lds_bytes(bool crc, bool dlv) {
+  return (crc ? kRvBytes : 0u) + (kRvBlock / 64) * kRvGroup * 8u * (1u + kRvHead) + (dlv ? kDlvTabBytes : 0u);
+}
+template <bool CRC, bool FILT, bool HOST, bool DLV>
+__device__ __forceinline__ void rv_check(const uint8_t* __restrict__ bytes, const uint64_t* __restrict__ off, uint64_t n,
+                                         uint32_t flags, uint8_t* __restrict__ okv, uint8_t* __restrict__ verdict,
+                                         const uint32_t* __restrict__ seg_len, const uint32_t* __restrict__ image,
+                                         uint32_t gsz, const RxFilter& filt, const uint32_t* __restrict__ gate,
+                                         uint32_t epoch, const lnxd::DlvPorts* ports, uint4* __restrict__ rec,
+                                         uint16_t* __restrict__ keys, char* lds) {
   // behind the ingress launch (lnx_ingress_verify_batch on a short-frame
   // batch, launch_ingress_verify): nothing to do unless it left this call's
   // epoch in the gate word
   if (gate && *gate != epoch) return;
   constexpr uint32_t kTabBytes = CRC ? kRvBytes : 0u;
   constexpr uint32_t kWaveBytes = kRvGroup * 8u * (1u + kRvHead);
-  __shared__ __attribute__((aligned(16))) char lds[kTabBytes + (kRvBlock / 64) * kWaveBytes];
+  constexpr uint32_t kPortTab = rv_lds_bytes(CRC, false);  // (a multiple of 16)
+  if constexpr (DLV) {
+    uint16_t* tab = reinterpret_cast<uint16_t*>(lds + kPortTab);
+    for (uint32_t i = threadIdx.x; i < 2u * lnxd::kPortsMax; i += kRvBlock)
+      tab[i] = i < lnxd::kPortsMax ? ports->tcp[i] : ports->udp[i - lnxd::kPortsMax];
+    if constexpr (!CRC) __syncthreads();
+  }
   if constexpr (CRC) {
     const uint32_t t = threadIdx.x;
     for (uint32_t vi = t; vi < 2048u; vi += kRvBlock) {
@@ -780,8 +803,61 @@ rx_verify_kernel(const uint8_t* __restrict__ bytes, const uint64_t* __restrict__
       if (okv) okv[f] = (uint8_t)rk.x;  // (null: the verdicts alone, for lnx_ingress_verify_batch)
       verdict[f] = (uint8_t)v;
     }
+    if constexpr (DLV) {
+      // ---- delivery: the frame's record and bucket key (a lane past the group has L = 0: no field is read)
+      const uint8_t* hb = reinterpret_cast<const uint8_t*>(head + kRvHead * kk);
+      auto dbyt = [&](uint32_t o) -> uint32_t {  // the byte at frame offset o < L
+        const uint32_t a = o + mis;              // byte of the window
+        if (a < 8u * kRvHead) return hb[a];
+        return (rv_ld32(reinterpret_cast<const uint32_t*>(base2) + (a >> 2)) >> (8u * (a & 3u))) & 0xFFu;
+      };
+      auto dbe16 = [&](uint32_t o) -> uint32_t { return (dbyt(o) << 8) | dbyt(o + 1u); };
+      lnxd::DlvPlan r = lnxd::dlv_parse(L, v, CRC ? (int32_t)rk.x : -1, filt, dbe16, dbyt);
+      // nodeByPort's first match: the lane scans its frame's table eight entries
+      // a step, in ascending order.  The trip count is the wave's: at most
+      // ceil(max(n_tcp, n_udp) / 8) steps, fewer once no lane is still looking.
+      int32_t k = (int32_t)lnxd::kPortsMax;
+      if (ports->on) {
+        const uint32_t nt = ports->n_tcp < lnxd::kPortsMax ? ports->n_tcp : lnxd::kPortsMax;
+        const uint32_t nu = ports->n_udp < lnxd::kPortsMax ? ports->n_udp : lnxd::kPortsMax;
+        const uint32_t steps = ((nt > nu ? nt : nu) + 7u) >> 3;
+        const uint32_t cnt = r.lookup == 6 ? nt : r.lookup == 17 ? nu : 0u;
+        const char* tab = lds + kPortTab + (r.lookup == 6 ? 0u : 2u * lnxd::kPortsMax);
+        k = -1;
+        for (uint32_t c = 0; c < steps; ++c) {
+          if (__builtin_amdgcn_ballot_w64(k < 0 && 8u * c < cnt) == 0) break;  // (wave-uniform)
+          const uint4 w4 = *reinterpret_cast<const uint4*>(tab + 16u * c);
+          const uint32_t w[4] = {w4.x, w4.y, w4.z, w4.w};
+          int32_t kc = -1;
+#pragma unroll
+          for (int j = 7; j >= 0; --j) {
+            const uint32_t port = (j & 1) ? w[j >> 1] >> 16 : w[j >> 1] & 0xFFFFu, i = 8u * c + (uint32_t)j;
+            kc = i < cnt && port == r.dst_port ? (int32_t)i : kc;
+          }
+          k = k < 0 ? kc : k;
+        }
+      }
+      lnxd::dlv_finish(r, k);
+      if (live) {
+        uint32_t w[4];
+        lnxd::dlv_pack(r, w);
+        rec[f] = uint4{w[0], w[1], w[2], w[3]};
+        if (keys) keys[f] = (uint16_t)lnxd::dlv_bucket(r);
+      }
+    }
     __builtin_amdgcn_wave_barrier();  // the next group rewrites res and head
   }
+}
+
+template <bool CRC, bool FILT, bool HOST>
+__global__ void __launch_bounds__(kRvBlock)
+rx_verify_kernel(const uint8_t* __restrict__ bytes, const uint64_t* __restrict__ off, uint64_t n, uint32_t flags,
+                 uint8_t* __restrict__ okv, uint8_t* __restrict__ verdict, const uint32_t* __restrict__ seg_len,
+                 const uint32_t* __restrict__ image, uint32_t gsz, RxFilter filt, const uint32_t* __restrict__ gate,
+                 uint32_t epoch) {
+  __shared__ __attribute__((aligned(16))) char lds[rv_lds_bytes(CRC, false)];
+  rv_check<CRC, FILT, HOST, false>(bytes, off, n, flags, okv, verdict, seg_len, image, gsz, filt, gate, epoch, nullptr,
+                                   nullptr, nullptr, lds);
 }
 
 // ------------------------------------------------------------------ transmit
@@ -1220,3 +1296,57 @@ hipError_t launch_rx_verify(const uint8_t* bytes, const uint64_t* off, uint64_t 
 }
 
 }  // namespace lnx
+
+// ------------------------------------------------------- receive check + delivery
+// The receive check that also writes each frame's delivery record and bucket
+// key (lnx_rx_verify_deliver_batch and the ring's deliver entries, DESIGN.md
+// §3.18): lnx::rv_check with DLV.  In namespace lnxd with the other delivery
+// kernels: the product library's kernels in namespace lnx stay the shipped set.
+namespace lnxd {
+
+template <bool CRC, bool FILT, bool HOST>
+__global__ void __launch_bounds__(lnx::kRvBlock)
+rx_verify_deliver_kernel(const uint8_t* __restrict__ bytes, const uint64_t* __restrict__ off, uint64_t n, uint32_t flags,
+                         uint8_t* __restrict__ okv, uint8_t* __restrict__ verdict,
+                         const uint32_t* __restrict__ seg_len, const uint32_t* __restrict__ image, uint32_t gsz,
+                         lnx::RxFilter filt, DlvPorts ports, uint4* __restrict__ rec, uint16_t* __restrict__ keys) {
+  __shared__ __attribute__((aligned(16))) char lds[lnx::rv_lds_bytes(CRC, true)];
+  lnx::rv_check<CRC, FILT, HOST, true>(bytes, off, n, flags, okv, verdict, seg_len, image, gsz, filt, nullptr, 0u, &ports,
+                                       rec, keys, lds);
+}
+
+// as launch_rx_verify (the same grid and groups); ports NULL: no tables; keys NULL: the records alone
+hipError_t launch_rx_verify_deliver(const uint8_t* bytes, const uint64_t* off, uint64_t n, uint32_t flags, bool fcs,
+                                    uint8_t* ok, uint8_t* verdict, const uint32_t* seg_len,
+                                    const lnx::RxFilter* filter, const lnx_rx_ports* ports, lnx_rx_delivery* rec,
+                                    uint16_t* keys, const uint32_t* image, int num_cus, hipStream_t stream,
+                                    bool host) {
+  lnx::RxFilter filt{};
+  if (filter) filt = *filter;
+  if (n == 0) return hipSuccess;
+  const DlvPorts pt = dlv_ports_of(ports);
+  constexpr uint64_t kWaves = lnx::kRvBlock / 64;
+  uint64_t grid = (n + kWaves * lnx::kRvGroup - 1) / (kWaves * lnx::kRvGroup);
+  if (grid > (uint64_t)num_cus) grid = (uint64_t)num_cus;
+  const uint32_t gsz = lnx::balanced_group(n, grid * kWaves, lnx::kRvGroup);
+#define LNX_RVD(C, F, H)                                                                                          \
+  hipLaunchKernelGGL((rx_verify_deliver_kernel<C, F, H>), dim3((unsigned)grid), dim3(lnx::kRvBlock), 0, stream, bytes, \
+                     off, n, flags, ok, verdict, seg_len, image, gsz, filt, pt, reinterpret_cast<uint4*>(rec), keys)
+  if (host) {
+    if (fcs) {
+      if (filt.on) LNX_RVD(true, true, true); else LNX_RVD(true, false, true);
+    } else {
+      if (filt.on) LNX_RVD(false, true, true); else LNX_RVD(false, false, true);
+    }
+  } else {
+    if (fcs) {
+      if (filt.on) LNX_RVD(true, true, false); else LNX_RVD(true, false, false);
+    } else {
+      if (filt.on) LNX_RVD(false, true, false); else LNX_RVD(false, false, false);
+    }
+  }
+#undef LNX_RVD
+  return hipGetLastError();
+}
+
+}  // namespace lnxd
