@@ -562,6 +562,74 @@ int lnx_rx_verify_deliver_batch(const uint8_t* d_bytes, const uint64_t* d_off, u
                                 uint8_t* d_verdict, lnx_rx_delivery* d_rec, uint32_t* d_order, uint32_t* d_count,
                                 void* d_ws, void* stream);
 
+/* RST replies for SYNs to closed ports: the other side effect
+ * of StackPorts.Demux on a TCP miss (internet/stack-ports.go:70-82).  A frame
+ * queues an entry when its delivery record has LNX_DLV_RST and the version
+ * nibble of its byte 14 is 4 (RSTQueue.Queue keeps 4-byte addresses only,
+ * tcp/rst.go:22-33; an IPv6 SYN gets no RST); the entry becomes the 54 header
+ * bytes RSTQueue.Drain, encapsulate4 and StackEthernet.Encapsulate write
+ * (tcp/rst.go:38-63, internet/stack-ip4.go:178-231,
+ * internet/stack-ethernet.go:170-217), padded to 60 bytes, with LNX_TX_FCS its
+ * LE FCS behind them.  RSTQueue's bound of four entries and its last-in
+ * first-out drain are NOT restated: the batch entry makes the reply of every
+ * queueing frame, in arrival order, up to `cap`, and reports how many it left
+ * out. */
+typedef struct lnx_rst_cfg {
+  uint8_t mac[6];     /* StackEthernet's MAC: the source */
+  uint8_t gw_mac[6];  /* its gateway MAC: the destination */
+  uint8_t ip4[4];     /* stackip4's address */
+  uint32_t flags;     /* LNX_TX_FCS or 0 */
+} lnx_rst_cfg;
+typedef struct lnx_tcp_rst {  /* rstEntry, tcp/rst.go:12-19 */
+  uint8_t remote_addr[4];
+  uint16_t remote_port, local_port;
+  uint32_t seq, ack;
+  uint16_t flags;  /* tcp.Flags; the frame carries flags & 0x1ff */
+  uint16_t zero;
+} lnx_tcp_rst;
+
+/* The IP IDs of the next n packets of a stack whose ipID is `ip_id`
+ * (internet/stack-ip4.go:189-195, internal/prand.go:4-10): out[0] =
+ * Prand16((ip_id + 1) ^ ip4_first), out[k] the same step from out[k - 1].
+ * After sending m of them the stack's ipID is out[m - 1]. */
+void lnx_ip4_id_chain(uint8_t ip4_first, uint16_t ip_id, uint64_t n, uint16_t* out);
+/* The entry frame[0 : len] (FCS stripped) queues under its record: 1 with *out
+ * written, 0 for none (*out untouched), LNX_EINVAL for a NULL rec or out or a
+ * NULL frame with len > 0.  Only len bounds what is read: a record whose
+ * l4_off + 8 > len, or len < 30, queues nothing. */
+int lnx_rx_rst_entry(const uint8_t* frame, size_t len, const lnx_rx_delivery* rec, lnx_tcp_rst* out);
+/* The reply of one entry with IP ID ip_id: all 64 bytes of out are written
+ * (60..63 zero without LNX_TX_FCS), *len = 64 with LNX_TX_FCS, else 60.
+ * LNX_EINVAL for a NULL pointer or an unknown bit in cfg->flags. */
+int lnx_tcp_rst_frame(const lnx_rst_cfg* cfg, const lnx_tcp_rst* entry, uint16_t ip_id, uint8_t out[64],
+                      uint32_t* len);
+
+/* The replies of a batch, chained behind lnx_rx_deliver_batch /
+ * lnx_rx_verify_deliver_batch on the same d_off (any order; an end below its
+ * start is an empty frame) and d_rec.  flags: LNX_RX_NO_FCS or 0 (frames carry
+ * their FCS).  Reply k answers the k-th queueing frame in index order, lies in
+ * the 64-byte slot d_reply + 64 k (d_reply 64-byte aligned; the frame's length
+ * is 64 with LNX_TX_FCS in cfg->flags, else 60), carries the IP ID d_ip_id[k]
+ * (`cap` entries) and d_src[k] = the index of the frame it answers.  d_n[0] =
+ * the replies written = min(wanted, cap), d_n[1] = wanted; slots and d_src
+ * entries at or past d_n[0] are not touched.  d_ws: lnx_rx_rst_ws_bytes(n)
+ * bytes of the caller's device memory, 4-byte aligned.  Three launches, none
+ * waiting for another workgroup and no global atomics: every output is a pure
+ * function of the inputs.  n == 0: LNX_OK with d_n zeroed (a NULL d_n: nothing
+ * to do); cap == 0: d_n alone is written.  LNX_EINVAL: n >= 2^32, a NULL
+ * pointer with work to do, an unknown flag bit on either flags word, a
+ * misaligned d_reply.  Asynchronous on `stream`; retains nothing, never
+ * synchronises the device and uses none of the library's per-stream scratch. */
+uint64_t lnx_rx_rst_ws_bytes(uint64_t n);
+int lnx_rx_rst_reply_batch(const uint8_t* d_bytes, const uint64_t* d_off, uint64_t n, uint32_t flags,
+                           const lnx_rx_delivery* d_rec, const lnx_rst_cfg* cfg, const uint16_t* d_ip_id, uint64_t cap,
+                           uint8_t* d_reply, uint32_t* d_src, uint32_t* d_n, void* d_ws, void* stream);
+/* The same frames from explicit entries (the RSTs tcp.Listener queues on the
+ * host, tcp/listener.go:221,228): reply k = lnx_tcp_rst_frame(cfg, d_entry[k],
+ * d_ip_id[k]) in the slot d_reply + 64 k.  n == 0: LNX_OK. */
+int lnx_tcp_rst_frames_batch(const lnx_rst_cfg* cfg, const lnx_tcp_rst* d_entry, uint64_t n, const uint16_t* d_ip_id,
+                             uint8_t* d_reply, void* stream);
+
 /* pcap's checksum re-verification over a batch: d_status[i] =
  * lnx_pcap_checksums(d_bytes[d_off[i] : d_off[i+1]]) for every Ethernet frame
  * (FCS stripped; an end offset below its start is an empty frame).  Four

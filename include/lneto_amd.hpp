@@ -355,6 +355,54 @@ inline int VerifyDeliverBatch(const uint8_t* d_frames, const uint64_t* d_off, ui
 }
 }  // namespace internet
 
+namespace tcp {
+// rstEntry (tcp/rst.go:12-19) and what RSTQueue.Queue / Drain make of it
+// (DESIGN.md §3.19).  The queue's bound of four entries and its last-in
+// first-out drain are not mirrored: the batch forms answer every entry in order.
+using RSTEntry = lnx_tcp_rst;
+constexpr uint16_t FlagRST = 0x04, FlagACK = 0x10;
+}  // namespace tcp
+
+namespace internet {
+// The stack's side of a reply: StackEthernet's MAC and gateway MAC, stackip4's
+// address, and StackEthernetConfig.AppendCRC32.
+struct RSTConfig {
+  uint8_t MAC[6] = {}, GatewayMAC[6] = {}, Addr4[4] = {};
+  bool AppendCRC32 = true;
+  lnx_rst_cfg ToC() const {
+    lnx_rst_cfg c{};
+    for (int i = 0; i < 6; ++i) c.mac[i] = MAC[i], c.gw_mac[i] = GatewayMAC[i];
+    for (int i = 0; i < 4; ++i) c.ip4[i] = Addr4[i];
+    c.flags = AppendCRC32 ? LNX_TX_FCS : 0u;
+    return c;
+  }
+};
+// stackip4's ipID over the next n packets (stack-ip4.go:189-195); the stack's ipID becomes out[n - 1]
+inline void IPIDChain(uint8_t addr4First, uint16_t ipID, uint64_t n, uint16_t* out) { lnx_ip4_id_chain(addr4First, ipID, n, out); }
+// StackPorts.Demux's RSTQueue.Queue for one frame under its record: true when an entry is queued
+inline bool RSTEntryOf(lneto::Bytes frame, const lnx_rx_delivery& rec, tcp::RSTEntry* out) {
+  return lnx_rx_rst_entry(frame.p, frame.n, &rec, out) == 1;
+}
+// RSTQueue.Drain inside encapsulate4 inside StackEthernet.Encapsulate: the frame's length, 0 on an argument error
+inline uint32_t RSTFrame(const RSTConfig& cfg, const tcp::RSTEntry& e, uint16_t ipID, uint8_t out[64]) {
+  const lnx_rst_cfg c = cfg.ToC();
+  uint32_t n = 0;
+  return lnx_tcp_rst_frame(&c, &e, ipID, out, &n) == LNX_OK ? n : 0u;
+}
+inline int RSTReplyBatch(const uint8_t* d_frames, const uint64_t* d_off, uint64_t n, const lnx_rx_delivery* d_rec,
+                         const RSTConfig& cfg, const uint16_t* d_ipID, uint64_t cap, uint8_t* d_reply, uint32_t* d_src,
+                         uint32_t* d_n, void* d_ws, bool noFCS = false, void* stream = nullptr) {
+  const lnx_rst_cfg c = cfg.ToC();
+  return lnx_rx_rst_reply_batch(d_frames, d_off, n, noFCS ? LNX_RX_NO_FCS : 0u, d_rec, &c, d_ipID, cap, d_reply, d_src, d_n,
+                                d_ws, stream);
+}
+inline int RSTFramesBatch(const RSTConfig& cfg, const tcp::RSTEntry* d_entry, uint64_t n, const uint16_t* d_ipID,
+                          uint8_t* d_reply, void* stream = nullptr) {
+  const lnx_rst_cfg c = cfg.ToC();
+  return lnx_tcp_rst_frames_batch(&c, d_entry, n, d_ipID, d_reply, stream);
+}
+}  // namespace internet
+
 namespace netdev {
 // Receive ring: bufferSelect-style pinned slots
 // (x/netdev/buffer.go:25-37) whose batches run through FCS verify and the

@@ -27,6 +27,8 @@ __all__ = [
     "CRC32_RESIDUE", "RxRing", "RxFilter", "RX_NO_FCS", "research_lib",
     "RxPorts", "DELIVERY_DTYPE", "rx_deliver", "rx_deliver_batch", "rx_deliver_ws_bytes", "rx_verify_deliver_batch",
     "H_ETH", "H_IP4", "H_IP6", "H_TCP", "H_UDP", "H_COUNT", "H_NONE", "DLV_RST", "DLV_IP6", "DLV_FCS",
+    "RstCfg", "TcpRst", "TX_FCS", "TCP_RST", "TCP_ACK", "ip4_id_chain", "rx_rst_entry", "tcp_rst_frame",
+    "rx_rst_ws_bytes", "rx_rst_reply_batch", "tcp_rst_frames_batch",
 ]
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -123,7 +125,50 @@ class RxPorts(ctypes.Structure):
         return r
 
 
+class RstCfg(ctypes.Structure):
+    """lnx_rst_cfg (include/lneto_amd.h): the stack's side of a RST reply —
+    StackEthernet's MAC and gateway MAC (internet/stack-ethernet.go:184,197),
+    stackip4's address (internet/stack-ip4.go:194) and whether the link layer
+    appends the CRC (:211-215).  Build it with RstCfg.make(mac=, gw_mac=, ip4=, fcs=)."""
+    _fields_ = [("mac", ctypes.c_uint8 * 6), ("gw_mac", ctypes.c_uint8 * 6), ("ip4", ctypes.c_uint8 * 4),
+                ("flags", ctypes.c_uint32)]
+
+    @classmethod
+    def make(cls, mac: bytes, gw_mac: bytes, ip4: bytes, fcs: bool = True) -> "RstCfg":
+        if len(mac) != 6 or len(gw_mac) != 6 or len(ip4) != 4:
+            raise LnetoError("RstCfg: mac 6 bytes, gw_mac 6, ip4 4")
+        c = cls()
+        c.mac[:] = list(mac)
+        c.gw_mac[:] = list(gw_mac)
+        c.ip4[:] = list(ip4)
+        c.flags = 2 if fcs else 0  # LNX_TX_FCS
+        return c
+
+
+class TcpRst(ctypes.Structure):
+    """lnx_tcp_rst (include/lneto_amd.h): rstEntry, tcp/rst.go:12-19."""
+    _fields_ = [("remote_addr", ctypes.c_uint8 * 4), ("remote_port", ctypes.c_uint16), ("local_port", ctypes.c_uint16),
+                ("seq", ctypes.c_uint32), ("ack", ctypes.c_uint32), ("flags", ctypes.c_uint16), ("zero", ctypes.c_uint16)]
+
+    @classmethod
+    def make(cls, remote_addr: bytes, remote_port: int, local_port: int, seq: int, ack: int, flags: int) -> "TcpRst":
+        if len(remote_addr) != 4:
+            raise LnetoError("TcpRst: remote_addr 4 bytes (RSTQueue.Queue keeps nothing else, tcp/rst.go:23)")
+        e = cls()
+        e.remote_addr[:] = list(remote_addr)
+        e.remote_port, e.local_port = remote_port & 0xFFFF, local_port & 0xFFFF
+        e.seq, e.ack, e.flags = seq & 0xFFFFFFFF, ack & 0xFFFFFFFF, flags & 0xFFFF
+        return e
+
+
 _sig = {
+    "lnx_ip4_id_chain": (None, [ctypes.c_uint8, ctypes.c_uint16, ctypes.c_uint64, _vp]),
+    "lnx_rx_rst_entry": (ctypes.c_int, [_vp, ctypes.c_size_t, _vp, _vp]),
+    "lnx_tcp_rst_frame": (ctypes.c_int, [_vp, _vp, ctypes.c_uint16, _vp, _vp]),
+    "lnx_rx_rst_ws_bytes": (ctypes.c_uint64, [ctypes.c_uint64]),
+    "lnx_rx_rst_reply_batch": (ctypes.c_int, [_vp, _vp, ctypes.c_uint64, ctypes.c_uint32, _vp, _vp, _vp, ctypes.c_uint64,
+                                              _vp, _vp, _vp, _vp, _vp]),
+    "lnx_tcp_rst_frames_batch": (ctypes.c_int, [_vp, _vp, ctypes.c_uint64, _vp, _vp, _vp]),
     "lnx_crc32_update": (ctypes.c_uint32, [ctypes.c_uint32, _u8p, ctypes.c_size_t]),
     "lnx_crc32": (ctypes.c_uint32, [_u8p, ctypes.c_size_t]),
     "lnx_crc32_combine": (ctypes.c_uint32, [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64]),
@@ -762,6 +807,121 @@ def rx_verify_deliver_batch(d_bytes, d_off, flags: int = 0, filter: RxFilter | N
         if ws is not None and stream is not None:
             ws.record_stream(stream)  # freed on return: not to be reused before the stream is done with it
     return ok, verdict, rec, (order[:n] if group else None), count
+
+
+# ------------------------------------------------------- RST replies
+TX_FCS = 2  # LNX_TX_FCS
+TCP_RST, TCP_ACK = 0x04, 0x10  # tcp.FlagRST, tcp.FlagACK
+
+
+def ip4_id_chain(ip4_first: int, ip_id: int, n: int) -> list:
+    """The IP IDs of the next n packets of a stack whose ipID is ip_id (lnx_ip4_id_chain):
+    Prand16((id + 1) ^ ip4[0]) step by step (internet/stack-ip4.go:189-195)."""
+    out = (ctypes.c_uint16 * max(n, 1))()
+    lib.lnx_ip4_id_chain(ip4_first & 0xFF, ip_id & 0xFFFF, n, out)
+    return list(out[:n])
+
+
+def _rst_entry_dict(e: TcpRst) -> dict:
+    return dict(remote_addr=bytes(e.remote_addr), remote_port=e.remote_port, local_port=e.local_port, seq=e.seq,
+                ack=e.ack, flags=e.flags)
+
+
+def rx_rst_entry(frame: bytes, rec) -> dict | None:
+    """The RST entry ONE frame (FCS stripped) queues under its delivery record
+    (lnx_rx_rst_entry), None for none.  rec: rx_deliver's dict, or the 16 record bytes."""
+    if isinstance(rec, dict):
+        raw = (rec["ip_end"].to_bytes(4, "little") + b"".join(rec[k].to_bytes(2, "little") for k in
+               ("handler", "l4_off", "src_port", "dst_port")) + bytes([rec["verdict"], rec["flags"]]) +
+               rec.get("zero", 0).to_bytes(2, "little"))
+    else:
+        raw = bytes(rec)
+    if len(raw) != 16:
+        raise LnetoError("rx_rst_entry: a delivery record is 16 bytes")
+    buf = bytes(frame)
+    e = TcpRst()
+    rc = lib.lnx_rx_rst_entry(buf, len(buf), raw, ctypes.byref(e))
+    if rc < 0:
+        _check(rc, "lnx_rx_rst_entry")
+    return _rst_entry_dict(e) if rc == 1 else None
+
+
+def tcp_rst_frame(cfg: RstCfg, entry, ip_id: int) -> bytes:
+    """The reply of one entry (a TcpRst, or a dict as rx_rst_entry gives) with IP ID
+    ip_id (lnx_tcp_rst_frame): 64 bytes with cfg's fcs, else 60."""
+    e = entry if isinstance(entry, TcpRst) else TcpRst.make(**entry)
+    out = (ctypes.c_uint8 * 64)()
+    n = ctypes.c_uint32(0)
+    _check(lib.lnx_tcp_rst_frame(ctypes.byref(cfg), ctypes.byref(e), ip_id & 0xFFFF, out, ctypes.byref(n)),
+           "lnx_tcp_rst_frame")
+    return bytes(out[:n.value])
+
+
+def rx_rst_ws_bytes(n: int) -> int:
+    """Bytes of device workspace lnx_rx_rst_reply_batch needs for n frames."""
+    return lib.lnx_rx_rst_ws_bytes(n)
+
+
+def rx_rst_reply_batch(d_bytes, d_off, d_rec, cfg: RstCfg, ip_id: int | None = None, ip_ids=None, cap: int | None = None,
+                       flags: int = 0, stream=None):
+    """The RST replies of a batch behind rx_deliver_batch / rx_verify_deliver_batch
+    on the same d_off and records (lnx_rx_rst_reply_batch): returns (reply, src,
+    n_written, n_wanted).  reply is [cap, 64] uint8, reply k in row k (its first
+    60 bytes without cfg's fcs), answering frame src[k] (int32, cap); rows at or
+    past n_written are left as allocated.  ip_id: the stack's ipID, from which
+    the chain of ``cap`` IDs is computed on the host and uploaded; or ip_ids: an
+    int16 device tensor of at least ``cap`` IDs.  cap defaults to the number of
+    frames.  flags: RX_NO_FCS or 0.  Synchronises to return the two counts."""
+    import torch
+    what = "lnx_rx_rst_reply_batch"
+    b = _Batch(what, [("d_bytes", d_bytes, "u8"), ("d_off", d_off, "i64"), ("d_rec", d_rec, "u8"),
+                      ("ip_ids", ip_ids, "i16?")], stream)
+    n = d_off.numel() - 1
+    if n < 0:
+        raise LnetoError(f"{what}: d_off holds no offset")
+    _need_len(what, "d_rec", d_rec, 16 * n)
+    if (ip_id is None) == (ip_ids is None):
+        raise LnetoError(f"{what}: give ip_id or ip_ids")
+    cap = n if cap is None else int(cap)
+    if ip_ids is None:
+        import numpy as np
+        ids = np.array(ip4_id_chain(cfg.ip4[0], ip_id, cap), dtype=np.uint16).view(np.int16)
+        ip_ids = torch.from_numpy(ids).to(b.device)
+    _need_len(what, "ip_ids", ip_ids, cap)
+    reply = torch.empty((cap, 64), dtype=torch.uint8, device=b.device)
+    src = torch.empty(cap, dtype=torch.int32, device=b.device)
+    d_n = torch.empty(2, dtype=torch.int32, device=b.device)  # (written by every call)
+    ws = torch.empty(rx_rst_ws_bytes(n), dtype=torch.uint8, device=b.device)
+    with b as s:
+        _check(lib.lnx_rx_rst_reply_batch(d_bytes.data_ptr(), d_off.data_ptr(), n, flags, d_rec.data_ptr(),
+                                          ctypes.byref(cfg), ip_ids.data_ptr() if cap else None, cap,
+                                          reply.data_ptr() if cap else None, src.data_ptr() if cap else None,
+                                          d_n.data_ptr(), ws.data_ptr(), s), what)
+        if stream is not None:
+            for t in (ws, ip_ids):
+                t.record_stream(stream)
+            stream.synchronize()
+        counts = d_n.cpu().numpy().view("uint32")
+    return reply, src, int(counts[0]), int(counts[1])
+
+
+def tcp_rst_frames_batch(cfg: RstCfg, d_entry, ip_ids, out=None, stream=None):
+    """The replies of explicit entries (lnx_tcp_rst_frames_batch): d_entry is
+    [n, 20] uint8, one lnx_tcp_rst a row (TcpRst / RST_ENTRY_DTYPE), ip_ids an int16
+    device tensor of n IDs; returns reply [n, 64] uint8."""
+    import torch
+    what = "lnx_tcp_rst_frames_batch"
+    b = _Batch(what, [("d_entry", d_entry, "u8"), ("ip_ids", ip_ids, "i16")], stream)
+    if d_entry.numel() % 20:
+        raise LnetoError(f"{what}: d_entry holds 20 bytes an entry")
+    n = d_entry.numel() // 20
+    _need_len(what, "ip_ids", ip_ids, n)
+    reply = _out(what, out, 64 * n, torch.uint8, "u8", b.device)
+    if n > 0:
+        with b as s:
+            _check(lib.lnx_tcp_rst_frames_batch(ctypes.byref(cfg), d_entry.data_ptr(), n, ip_ids.data_ptr(),
+                                                reply.data_ptr(), s), what)
+    return reply.view(-1)[:64 * n].view(n, 64)
 
 
 PCAP_IP_HDR_BAD, PCAP_PROTO_BAD = 1, 2  # LNX_PCAP_IP_HDR_BAD, LNX_PCAP_PROTO_BAD

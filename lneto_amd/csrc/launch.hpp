@@ -46,6 +46,16 @@ hipError_t launch_rx_verify_deliver(const uint8_t* bytes, const uint64_t* off, u
                                     bool host = false);
 }  // namespace lnxd
 
+// reply_kernel.hip: RST replies for SYNs to closed ports
+namespace lnxr {
+uint64_t rst_ws_bytes(uint64_t n);
+hipError_t launch_rst_reply(const uint8_t* bytes, const uint64_t* off, uint64_t n, uint32_t trim, const lnx_rx_delivery* rec,
+                            const lnx_rst_cfg& cfg, const uint16_t* ip_id, uint64_t cap, uint8_t* reply, uint32_t* src,
+                            uint32_t* d_n, void* ws, const uint32_t* image, hipStream_t stream);
+hipError_t launch_rst_frames(const lnx_rst_cfg& cfg, const lnx_tcp_rst* entry, uint64_t n, const uint16_t* ip_id,
+                             uint8_t* reply, const uint32_t* image, hipStream_t stream);
+}  // namespace lnxr
+
 namespace lnx {
 
 // api.cpp: the current device's images and CU count, and the thread's lnx_last_error

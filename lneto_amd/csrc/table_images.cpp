@@ -170,6 +170,17 @@ std::vector<uint32_t> build_rx_image() {
   return img;
 }
 
+// The RST reply image (table_layout.hpp kRstImgZ).
+std::vector<uint32_t> build_rst_image() {
+  std::vector<uint32_t> img(kRstImageDwords);
+  for (uint32_t p = 0; p < kRstLanes; ++p) {
+    const Z z(4 * (int64_t)(kRstLanes - p));
+    for (uint32_t i = 0; i < 8; ++i)
+      for (uint32_t v = 0; v < 16; ++v) img[rst_nib(p, i, v)] = z(v << (4 * i));
+  }
+  return img;
+}
+
 // The CRC32Search tables (table_layout.hpp k*Off).
 std::vector<uint32_t> build_search_tables() {
   std::vector<uint32_t> img(kSearchTableDwords);

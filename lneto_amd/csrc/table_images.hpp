@@ -11,5 +11,6 @@ const std::vector<uint32_t>& host_image();              // the rows images, comp
 std::vector<uint32_t> build_stage_image();              // table_layout.hpp: kStageImageDwords
 std::vector<uint32_t> build_rx_image();                 // kRxImageDwords
 std::vector<uint32_t> build_search_tables();            // kSearchTableDwords
+std::vector<uint32_t> build_rst_image();                // kRstImageDwords
 
 }  // namespace lnx

@@ -1,6 +1,7 @@
 // table_layout.hpp — dword layout of the table images that table_images.cpp
 // builds on the host and the kernels read from HBM: the staged lane streams'
-// image, the receive / transmit image and the CRC32Search tables.  (The CRC
+// image, the receive / transmit image, the CRC32Search tables and the RST
+// reply image.  (The CRC
 // rows' LDS images are in lds_layout.hpp.)  Each region starts where the one
 // before it ends; both sides take every offset from here.
 //
@@ -62,6 +63,14 @@ constexpr uint32_t kOctNibOff = kZ24Off + kByte4Dwords;                 // Z_48 
 constexpr uint32_t kOctLevOff = kOctNibOff + kBankCols * kNib8Dwords;   // Z_{192*2^k} byte tables, k < 3: the product's scan
 constexpr uint32_t kOctTabDwords = kOctLevOff + 3 * kByte4Dwords - kOctNibOff;  // (copied in one piece)
 constexpr uint32_t kSearchTableDwords = kOctNibOff + kOctTabDwords;
+
+// ---- the RST reply image (reply_kernel.hip, reply_host.cpp: reply_plan.hpp rst_fcs_part)
+constexpr uint32_t kRstLanes = 15;                                      // the dwords of a 60-byte frame
+constexpr uint32_t kRstImgZ = 0;                                        // Z_{4(15-p)} nibble tables, p < 15: dword p's share of the FCS
+constexpr uint32_t kRstImageDwords = kRstImgZ + kRstLanes * kNib8Dwords;
+// (an odd p keeps its nibble tables in swapped pairs: the sixteen lanes of a row, one p each, reach all 32 LDS banks)
+constexpr uint32_t rst_nib(uint32_t p, uint32_t i, uint32_t v) { return nib8_at(kRstImgZ + kNib8Dwords * p, i ^ (p & 1u), v); }
+static_assert(kRstImageDwords == 1920, "RST reply image");
 
 // the values every reader of these images was written against
 static_assert(kStageZ8Img == 5504 && kStageNibHiImg == 14720 && kStageImageDwords == 15872, "staged image");
