@@ -30,8 +30,9 @@ constexpr uint32_t kRecGridCap = 2048;         // workgroups of the records laun
 // at most 3 bytes into the window's first dword: 91 <= 128.
 constexpr uint32_t kWinDwords = 32, kWinBytes = 4 * kWinDwords, kWinFrame = kWinBytes - 3;
 
-constexpr int kGrpBlock = 256;                 // frames per chunk: one per thread
-constexpr uint32_t kGrpGridCap = 512;          // workgroups of the histogram / scatter launches
+// (kGrpBlock, kGrpGridCap and kScanWaves are restated in tests/test_deliver_gpu.py and tests/test_deliver_grid_mid.py)
+constexpr int kGrpBlock = 256;                 // frames per chunk: one per thread (tests: CHUNK)
+constexpr uint32_t kGrpGridCap = 512;          // workgroups of the histogram / scatter launches (tests: GRID_CAP)
 constexpr uint32_t kBuckets = kHCount + 1;     // handler ids, then the frames not delivered
 constexpr uint32_t kDeadKey = 2047;            // 11 key bits; no frame has it
 static_assert(kBuckets <= kDeadKey && kBuckets <= 5 * kGrpBlock, "bucket keys: 11 bits, five per thread in the scan");
@@ -140,7 +141,7 @@ deliver_hist_kernel(const uint16_t* __restrict__ keys, uint64_t n, uint32_t* __r
 // the bucket's size.  A workgroup takes 64 buckets (one a lane); its wave w
 // takes the workgroups [w seg, (w + 1) seg) of the histogram launch: all its
 // loads at once, the waves' totals joined through LDS.
-constexpr uint32_t kScanWaves = 16, kScanSeg = 32;
+constexpr uint32_t kScanWaves = 16, kScanSeg = 32;  // kScanWaves: SCAN_WAVES in tests/test_deliver_grid_mid.py
 static_assert(kGrpGridCap <= kScanWaves * kScanSeg, "the scan holds a wave's segment in registers");
 __global__ void __launch_bounds__(64 * kScanWaves)
 deliver_scan_kernel(uint32_t* __restrict__ hist, uint32_t G, uint32_t* __restrict__ count) {

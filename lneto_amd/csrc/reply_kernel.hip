@@ -24,10 +24,12 @@
 
 namespace lnxr {
 
-constexpr int kRpBlock = 256;                  // frames per chunk: one per thread
+// (kRpBlock and kRpGridCap are restated in tests/test_rst_reply_gpu.py and tests/test_rst_reply_grid_mid.py)
+constexpr int kRpBlock = 256;                  // frames per chunk: one per thread (tests: CHUNK)
 constexpr uint32_t kRpWaves = kRpBlock / 64, kRpRows = kRpBlock / 16;
-constexpr uint32_t kRpGridCap = 512;           // workgroups of the count / build launches
-constexpr uint32_t kRpFramesGridCap = 2048;    // ... of the explicit-entries launch (grid-strided past it)
+constexpr uint32_t kRpGridCap = 512;           // workgroups of the count / build launches (tests: GRID_CAP)
+// ... of the explicit-entries launch, grid-strided past it (FRAMES_GRID_CAP in tests/test_rst_reply_grid_mid.py)
+constexpr uint32_t kRpFramesGridCap = 2048;
 
 // Workgroup g of G owns the index slice [lo, hi): `per` consecutive chunks of
 // kRpBlock frames, per = ceil(chunks / G).  The count and the build launch use the same G.
