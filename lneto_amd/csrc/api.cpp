@@ -791,30 +791,11 @@ int lnx__crc32_variant(int var, const uint8_t* d_bytes, const uint64_t* d_off, u
   DeviceCtx* c = nullptr;
   int st = get_ctx(&c);
   if (st != LNX_OK) return st;
-  // 300 / 301: the staged lane streams (stage_kernel.hip), CRC / FCS verify,
-  // slicing-by-2 fold; 302 / 303: the same with the 16-column Z_4 fold;
-  // 304-307: 300-303 with 10 waves per workgroup instead of 8 (retired);
-  // 308 / 309: 302 / 303 with 766-frame blocks; 310 / 311: the slicing-by-8 fold;
-  // 312 / 313: the slicing-by-8 fold with the boundary correction deferred;
-  // 314 / 315: the slicing-by-8 fold with the boundary word patched per half;
-  // 316 / 317: 314 / 315 with each half folded as two chains of four units;
-  // 318 / 319 and 320 / 321: 314 / 315 with 190- and 254-frame blocks;
-  // 322 / 323: 314 / 315 with the next block's offsets loaded ahead;
-  // 324 / 325: 314 / 315 with 510-frame blocks; 326 / 327: 314 / 315 with 6 waves;
-  // 328 / 330: timing only (wrong results): 314 without the transpose writes,
-  // 314 with a two-op stand-in for the lookups; 332: 314 without the ending
-  // frames' capture and Z_c; 334: 314 without the carries; 340: the ring's
-  // loads alone; 342: loads + the LDS transpose (round 5)
-  // (all in stage_research.hip, the round-4 kernel; the product staged kernel
-  // with its round-5 dispatch is lnx_crc32_batch_ex(LNX_BATCH_SHORT_FRAMES))
-  hipError_t e = (var >= 300 && var <= 327) || var == 328 || var == 330 || var == 332 || var == 334 || var == 340 ||
-                         var == 342
-                     ? rs::launch_crc32_stage_research(d_bytes, d_off, n, d_crc, var & 1,
-                                          var == 342 ? 22 : var == 340 ? 21 : var == 334 ? 20 : var == 332 ? 19 : var == 330 ? 18 : var == 328 ? 17 : var >= 326 ? 16 : var >= 324 ? 15 : var >= 322 ? 14 : var >= 320 ? 13 : var >= 318 ? 12 : var >= 316 ? 11 : var >= 314 ? 10 : var >= 312 ? 9 : var >= 310 ? 8 : (var & 2) || var >= 308 ? 4 : 2,
-                                          var >= 304 && var < 308 ? 10 : 8, c->d_stage, c->num_cus,
-                                          static_cast<hipStream_t>(stream), var == 308 || var == 309)
-                     : launch_crc32_variant(var, d_bytes, d_off, n, d_crc, c->d_image, c->num_cus,
-                                            static_cast<hipStream_t>(stream), nullptr);
+  const rs::StageVariant* sv = rs::stage_variant(var);
+  hipError_t e = sv ? rs::launch_crc32_stage_research(d_bytes, d_off, n, d_crc, var & 1, sv->fold, sv->waves, c->d_stage,
+                                                      c->num_cus, static_cast<hipStream_t>(stream), sv->big_blocks)
+                    : launch_crc32_variant(var, d_bytes, d_off, n, d_crc, c->d_image, c->num_cus,
+                                           static_cast<hipStream_t>(stream), nullptr);
   if (e != hipSuccess) return hip_fail(e, "crc32 variant launch");
   return LNX_OK;
 }

@@ -49,6 +49,7 @@
 #include "lds_layout.hpp"
 #include "dispatch.hpp"
 #include "launch.hpp"
+#include "rows_cfg.hpp"
 #include "wave_util.hpp"
 
 // Cache-policy suffix of the streaming frame loads (e.g. " nt" for profiling
@@ -367,7 +368,6 @@ __device__ __forceinline__ void slot_wait(Word (&w)[KS], uint32_t& junk, uint32_
 // untouched with status 6 (ErrShortBuffer).  The CRC of the padded frame is
 // the frame's register advanced over the k = 60 - n pad bytes (zero_advance):
 // the pad is written, never read.
-enum class CrcMode : int { kCrc = 0, kVerify = 1, kAppend = 2 };
 constexpr uint32_t kMinFrame = 60;
 constexpr uint8_t kErrShortBuffer = 6;
 
@@ -545,9 +545,8 @@ struct WaveCtx {
 };
 
 // RL: lanes per row, KS: window steps per item, S: ring slots, CH: frames per
-// chunk, VAR: profiling knob (0 = product, 1 = loads +
-// bookkeeping only, 2 = lookups + bookkeeping on synthetic words).  Only VAR 0
-// is reachable from the C-ABI.
+// chunk, VAR: profiling probe (rows_cfg.hpp).  Only
+// Probe::kProduct is reachable from the C-ABI.
 //
 // Work distribution: the waves of a workgroup claim chunks of CH consecutive
 // frames from an LDS counter (one ds_add_rtn per chunk), so a wave that the
@@ -563,7 +562,7 @@ struct WaveCtx {
 // carries four frames.  Lane p then holds the registers of "virtual lanes"
 // v = 2p and 2p + 1 of a 32-virtual-lane row; all the window algebra below is
 // in virtual lanes.
-template <CrcMode MODE, int RL, int KS, int S, int CH, int VAR, bool SEG, int WL = 1, bool EDGE = true, int NSR = 0>
+template <CrcMode MODE, int RL, int KS, int S, int CH, Probe VAR, bool SEG, int WL = 1, bool EDGE = true, int NSR = 0>
 __device__ __forceinline__ void rows_body(const char* lds, const Lanes& L, const WaveCtx& cx) {
   constexpr uint32_t NR = 64 / RL;  // rows (frames in flight) per wave
   constexpr uint32_t VL = RL * WL;  // virtual lanes per row
@@ -601,11 +600,11 @@ __device__ __forceinline__ void rows_body(const char* lds, const Lanes& L, const
   constexpr uint32_t kEndAlign = kLine ? 128u : WL == 4 ? 16u : 4u;
   static_assert(S >= 1 && NR <= (uint32_t)CH && CH <= 64 && S * NR <= 64, "chunk and bounds window shape");
   static_assert(KS >= 2 && (KS - 1) * SB <= 4095, "buffer immediate offset");
-  constexpr int kLoads = (VAR == 2 ? 0 : KS) + 3;  // steps, junk, start + end
+  constexpr int kLoads = (VAR == Probe::kMathOnly ? 0 : KS) + 3;  // steps, junk, start + end
   // bounds window: only lanes < S*NR are ever read back (ds_bpermute index
-  // li < S*NR); the other lanes' offset loads are out of range (VAR 3: all 64
-  // lanes load, the earlier behaviour, for A/B timing)
-  constexpr uint32_t kWin = VAR == 3 ? 64u : S * NR;
+  // li < S*NR); the other lanes' offset loads are out of range (kWindow64: all
+  // 64 lanes load, the earlier behaviour, for A/B timing)
+  constexpr uint32_t kWin = VAR == Probe::kWindow64 ? 64u : S * NR;
   constexpr int kPending = (S - 1) * kLoads;       // loads issued after a slot's own
   const uint32_t lane = L.lane, p = L.p, row = L.row, bu0 = L.bu0, bu1 = L.bu1, bf = L.bf, bt = L.bt;
   const uint32_t nfb = cx.nfb, o0_lo = cx.o0_lo, adj = cx.adj;
@@ -693,9 +692,9 @@ __device__ __forceinline__ void rows_body(const char* lds, const Lanes& L, const
   //    writes in bursts (+2.4 % at 1500 B, +1.6 % at 9000 B).  Flushing when
   //    full alone wrote 16-byte pieces of lines at uncorrelated times, and
   //    the partial-line writebacks made it 3 % slower than per-slot stores.
-  // VAR 4: one store per slot (A/B); VAR 5: clock windows for 4-lane rows too.
-  constexpr bool kHold = VAR != 4;
-  constexpr bool kWinFlush = kHold && (RL >= 16 || VAR == 5);
+  // kStoreAtOnce: one store per slot (A/B); kFlush4: clock windows for 4-lane rows too.
+  constexpr bool kHold = VAR != Probe::kStoreAtOnce;
+  constexpr bool kWinFlush = kHold && (RL >= 16 || VAR == Probe::kFlush4);
   constexpr int kWinLog = 12;
   uint32_t hf = 0, hv = 0, pc = 0;
   uint32_t he = 0, hpl = 0;  // kAppend: FCS position and new length of the held frame
@@ -757,7 +756,7 @@ __device__ __forceinline__ void rows_body(const char* lds, const Lanes& L, const
     const uint32_t jl = kSkip ? VL - 1u - (rt >> 2) : VL - 1u;
     const uint32_t jv = ends && p == jl / WL && (rt & 3u) != 0 ? rea - SB + (jl << 2) : kOOB;
     rj += ns;
-    if constexpr (VAR == 2) {
+    if constexpr (VAR == Probe::kMathOnly) {
 #pragma unroll
       for (int k = 0; k < KS; ++k) {
         if constexpr (WL == 4) {
@@ -865,7 +864,7 @@ __device__ __forceinline__ void rows_body(const char* lds, const Lanes& L, const
       if (k == 1 && h == 0) x ^= m1;
       return x;
     };
-    if constexpr (VAR == 1) {
+    if constexpr (VAR == Probe::kLoadsOnly) {
 #pragma unroll
       for (int k = 0; k < KS; ++k)
 #pragma unroll
@@ -991,7 +990,7 @@ __device__ __forceinline__ void rows_body(const char* lds, const Lanes& L, const
         const bool lv = fin.last && fin.f != kNoFrame;
         if constexpr (kHold)
           R = append_pad<RL, kImg>(lds, Lz, lv, n, R, cx.ap.data_base + fin.e, cx.ap.cap, kpad);
-        else  // VAR 4: the FCS, length and status stored at once (A/B)
+        else  // kStoreAtOnce: the FCS, length and status stored at once (A/B)
           append_tail<RL, kImg>(lds, Lz, lv, n, R, cx.ap.data_base + fin.e, cx.ap.cap, cx.ap.lenw + fin.f,
                                 cx.ap.stat + fin.f);
       }
@@ -1084,7 +1083,7 @@ __device__ __forceinline__ void rows_body(const char* lds, const Lanes& L, const
 // SEG: segment mode (frame i = bytes[start[i] : start[i] + len[i]], in address
 // order, not overlapping: ring slots, lnx_crc32_segments / the TX FCS append):
 // lanes 0..3 load the chunk's starts and lengths instead of five offsets.
-template <CrcMode MODE, int KS, int VAR, int WL = 2, bool JM = true, int EP = 0, bool SEG = false>
+template <CrcMode MODE, int KS, Probe VAR, int WL = 2, bool JM = true, int EP = 0, bool SEG = false>
 __device__ __forceinline__ void lines_body(const char* lds, const Lanes& L, const WaveCtx& cx) {
   static_assert(WL == 1 || WL == 2, "words per lane");
   constexpr uint32_t RL = 32 / WL;  // lanes per row
@@ -1192,7 +1191,7 @@ __device__ __forceinline__ void lines_body(const char* lds, const Lanes& L, cons
   };
   auto issue = [&](const Rowp& r) {
     const uint32_t voff = r.J ? r.ws + p * (4u * WL) : kOOB;
-    if constexpr (VAR == 2) {
+    if constexpr (VAR == Probe::kMathOnly) {
 #pragma unroll
       for (int k = 0; k < KS; ++k) w[k] = (Word)((uint64_t)(voff * 0x9E3779B1u + k) * 0x100000001ull);
     } else {
@@ -1220,7 +1219,7 @@ __device__ __forceinline__ void lines_body(const char* lds, const Lanes& L, cons
     }
   };
 
-  // VAR 7 (kAppend, two-word rows; A/B, not the product): the FCS is written
+  // kSectorStore (kAppend, two-word rows; A/B, not the product): the FCS is written
   // with the whole 64-byte sector that holds it (the frame's last line is in
   // the lanes' registers: the bytes before the FCS are the frame's, the ones
   // after it the slot's, rewritten as loaded).  In tools/ubench/scatter_write.hip
@@ -1228,7 +1227,7 @@ __device__ __forceinline__ void lines_body(const char* lds, const Lanes& L, cons
   // this kernel they measured 2 % slower than the held dword
   // (profiles/r3j_fcs_append_sector_ab.txt): every TCC write request became a
   // 64-byte one, and the time per write stayed.
-  constexpr bool kSector = MODE == CrcMode::kAppend && WL == 2 && VAR == 7;
+  constexpr bool kSector = MODE == CrcMode::kAppend && WL == 2 && VAR == Probe::kSectorStore;
   struct Fin {
     uint32_t r0, r1, junk, f, n, t, e;
     uint64_t tl;  // kSector: this lane's 8 bytes of the frame's last line
@@ -1272,7 +1271,7 @@ __device__ __forceinline__ void lines_body(const char* lds, const Lanes& L, cons
     };
     uint32_t reg[WL] = {};
     uint64_t tl = 0;  // kSector: step J - 1's 8 bytes of this lane
-    if constexpr (VAR == 1) {
+    if constexpr (VAR == Probe::kLoadsOnly) {
 #pragma unroll
       for (int k = 0; k < KS; ++k)
 #pragma unroll
@@ -1396,7 +1395,7 @@ __device__ __forceinline__ void lines_body(const char* lds, const Lanes& L, cons
     R = n != 0 ? R : 0u;
     if (n < 4) R ^= (uint32_t)(0xFFFFFFFFull >> (8 * n));
     uint32_t kpad = 0;
-    if constexpr (MODE == CrcMode::kAppend && VAR == 4) {  // the FCS, length and status stored at once (A/B)
+    if constexpr (MODE == CrcMode::kAppend && VAR == Probe::kStoreAtOnce) {  // the FCS, length and status stored at once (A/B)
       append_tail<WL == 2 ? 16 : 32, 32>(lds, L, live, n, R, cx.ap.data_base + fin.e, cx.ap.cap, cx.ap.lenw + fin.f,
                                          cx.ap.stat + fin.f);
       return;
@@ -1491,11 +1490,11 @@ __device__ __forceinline__ void lines_body(const char* lds, const Lanes& L, cons
 }
 
 // ------------------------------------------------------------------ kernel
-// Row width per workgroup from its frames' mean length (RLF = 0): 4-lane rows
-// below kShortMean, 32-lane rows from kLineMean on, 16-lane rows with MIDW
-// words per lane between; or forced (RLF = 4 / 16 / 32, profiling).  Item
-// size, ring depth and chunk: KSW, SW, CHW for 32-lane rows, KSM, SM, CHM
-// for 16-lane rows, KS4, S4, CH4 for 4-lane rows.
+// Row width per workgroup from its frames' mean length (Width::kPerSlice):
+// 4-lane rows below kShortMean, 32-lane rows from kLineMean on, 16-lane rows
+// in the form RowsCfg::mid names between; or forced (profiling).  Item size,
+// ring depth and chunk: ksw, sw, chw for 32-lane rows, ksm, sm, chm for
+// 16-lane rows, ks4, s4, ch4 for 4-lane rows (rows_cfg.hpp).
 //
 // 32-lane rows and 16-lane rows of two words per lane both read whole lines
 // with nt loads (loads alone: 6.4 TB/s at 1500 B against 6.0 for one-word
@@ -1503,11 +1502,11 @@ __device__ __forceinline__ void lines_body(const char* lds, const Lanes& L, cons
 // 1500 B (one 13-line item per frame) their per-frame finish costs more:
 // 32-lane rows finish 2 frames per wave-slot where 16-lane rows finish 4
 // (VALU-bound, 4.9 TB/s), and two-word rows apply F to 32 registers per frame
-// (5.7-5.8 TB/s against 5.9 for one-word rows).  So MIDW = 1 in the product
+// (5.7-5.8 TB/s against 5.9 for one-word rows).  So the product's 16-lane rows of frames over kLeanMean take one word per lane
 // (profiles/r1f_line_rows_variants.txt).
 constexpr uint64_t kLineMean = 4096;
 // Lean line rows (lines_body) from kShortMean up to this mean frame length
-// (MIDW = 4): one frame per row per slot needs frames of at most KSL lines.
+// (Mid::kLeanShort): one frame per row per slot needs frames of at most ksl lines.
 constexpr uint64_t kLeanMean = 1600;
 // Offsets mode: a slice of at most this many frames has every pair of its
 // offsets checked, whatever its frames' length and its sample; a longer one
@@ -1576,16 +1575,19 @@ __device__ __forceinline__ void pairs_check(uint64_t i0, uint64_t fb1, const uin
   }
 }
 
-template <CrcMode MODE, int VAR = 0, int RLF = 0, int KSW = 24, int SW = 1, int KS4 = 16, int S4 = 2,
-          int CHW = 4, int CH4 = 32, bool SEG = false, int MIDW = 4, int KSM = 24, int SM = 1, int CHM = 4,
-          int KSL = 13, int LWL = 2, bool LJM = true, int LEP = 1, bool REDGE = true, int NSR4 = 4, int NW4 = 1,
-          int STR = 0>
+// C: which instance this is (rows_cfg.hpp explains every field).
+template <RowsCfg C>
 __global__ void __launch_bounds__(kBlockThreads, 1)
 crc32_rows_kernel(const uint8_t* bytes,  /* not __restrict__: kAppend writes the FCS through it */ const uint64_t* __restrict__ off, uint64_t nframes,
                   uint64_t frames_per_wave, const uint4* __restrict__ images, void* __restrict__ out,
                   uint64_t* __restrict__ timeline,
                   const uint32_t* seg_len, uint32_t cap, uint32_t policy, uint32_t* __restrict__ stage_flag,
                   uint32_t epoch) {
+  constexpr CrcMode MODE = C.mode;
+  constexpr Probe VAR = C.probe;
+  constexpr Stream STR = C.stream;
+  constexpr bool SEG = C.seg;
+  constexpr int RLF = (int)C.width, NW4 = C.nw4;
   __shared__ __attribute__((aligned(16))) uint32_t lds_words[kLdsDwords];
   // profiling (tools/prof/timeline.py): per wave, 100 MHz clock at entry,
   // after the LDS image copy and at exit; null in the product path
@@ -1650,22 +1652,18 @@ crc32_rows_kernel(const uint8_t* bytes,  /* not __restrict__: kAppend writes the
     }
   }
   int rl = RLF;
-  // MIDW (16-lane rows): 1 = one word per lane, 2 = two words, 3 = lean line
-  // rows, 4 = lean line rows below kLeanMean, one word per lane above
-  // (24-line lean items for 1600-3000 B were tried: w[24] pushed the kernel
-  // past its VGPR budget into scratch)
-  bool lean = MIDW == 3;
+  bool lean = C.mid == Mid::kLean;
   if constexpr (RLF == 0) {
     const uint64_t nf_ = fb1 - fb0, nb_ = ob1 > ob0 ? ob1 - ob0 : 0;
     rl = nf_ == 0 || nb_ < kShortMean * nf_ ? 4 : nb_ < kLineMean * nf_ ? 16 : 32;
-    if (MIDW == 4) lean = rl == 16 && nb_ < kLeanMean * nf_;
+    if (C.mid == Mid::kLeanShort) lean = rl == 16 && nb_ < kLeanMean * nf_;
   }
   const bool narrow = rl == 4;
   // whole-line windows: the RL = 32 image
-  const bool line = rl == 32 || (rl == 16 && (MIDW == 2 || lean));
+  const bool line = rl == 32 || (rl == 16 && (C.mid == Mid::kTwoWords || lean));
   // streaming rows (research/stream_rows.hpp) for the narrow rows' frames in offsets
   // mode, when the slice's bytes fit 31-bit buffer offsets from a line-aligned base
-  bool strm = STR != 0 && narrow && !SEG && MODE != CrcMode::kAppend;
+  bool strm = STR != Stream::kNone && narrow && !SEG && MODE != CrcMode::kAppend;
   if (strm) {
     const uint64_t nb_ = ob1 > ob0 ? ob1 - ob0 : 0;
     const uint64_t adj_ = (reinterpret_cast<uintptr_t>(bytes) + ob0) & 127u;
@@ -1674,7 +1672,7 @@ crc32_rows_kernel(const uint8_t* bytes,  /* not __restrict__: kAppend writes the
   // the row width whose image the workgroup holds (4-lane rows of four words
   // per lane fold 16 virtual lanes: the RL = 16 image)
   int img_rl = strm ? 0 : line ? 32 : (narrow && NW4 == 4) ? 16 : rl;
-  const ImageRegs image = image_fetch(images, image_index(strm ? (STR == 3 ? 10 : STR == 2 ? 9 : 8) : img_rl));
+  const ImageRegs image = image_fetch(images, image_index(strm ? (STR == Stream::kLanes ? 10 : STR == Stream::kRows4 ? 9 : 8) : img_rl));
   image_store(lds_words, image);
   // Which slices get the check: every slice of at most kCheckFrames frames;
   // a longer one when its sample shows a reversed pair (slice_kind sends such
@@ -1801,12 +1799,12 @@ crc32_rows_kernel(const uint8_t* bytes,  /* not __restrict__: kAppend writes the
     const WaveCtx cx = ctx_of(own);
     asm volatile("s_nop 4" ::: "memory");  // descriptors may be SGPRs just written by VALU readfirstlane
 #ifdef LNX_RESEARCH
-    if constexpr (STR != 0 && !SEG && MODE != CrcMode::kAppend) {
+    if constexpr (STR != Stream::kNone && !SEG && MODE != CrcMode::kAppend) {
       if (strm) {
-        if constexpr (STR == 3) {
+        if constexpr (STR == Stream::kLanes) {
           lanes_body<MODE, VAR>(lds, L, cx);
         } else {
-          constexpr int RLS = STR == 2 ? 4 : 8;
+          constexpr int RLS = STR == Stream::kRows4 ? 4 : 8;
           L.p = lane & (RLS - 1u), L.row = lane / RLS;
           stream_body<MODE, VAR, RLS>(lds, L, cx);
         }
@@ -1815,7 +1813,8 @@ crc32_rows_kernel(const uint8_t* bytes,  /* not __restrict__: kAppend writes the
       }
     }
 #else
-    static_assert(STR == 0 && VAR == 0, "variants are built into the research library only");
+    static_assert(STR == Stream::kNone && VAR == Probe::kProduct,
+                  "probes and streaming forms are built into the research library only");
 #endif
     if (narrow) {
 #ifdef LNX_RESEARCH
@@ -1825,168 +1824,80 @@ crc32_rows_kernel(const uint8_t* bytes,  /* not __restrict__: kAppend writes the
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #endif
       L.p = lane & 3u, L.row = lane >> 2;
-      rows_body<MODE, 4, KS4, S4, CH4, VAR, SEG, NW4, true, NSR4>(lds, L, cx);
+      rows_body<MODE, 4, C.ks4, C.s4, C.ch4, VAR, SEG, NW4, true, C.nsr4>(lds, L, cx);
     } else if (rl == 16 && lean) {
-      // lean rows: 16 lanes x two words (LWL = 2) or 32 lanes x one word (LWL = 1)
-      L.p = lane & (32u / LWL - 1u), L.row = lane / (32u / LWL);
-      lines_body<MODE, KSL, VAR, LWL, LJM, LEP, SEG>(lds, L, cx);
+      // lean rows: 16 lanes x two words (lwl = 2) or 32 lanes x one word (lwl = 1)
+      L.p = lane & (32u / C.lwl - 1u), L.row = lane / (32u / C.lwl);
+      lines_body<MODE, C.ksl, VAR, C.lwl, C.ljm, C.lep, SEG>(lds, L, cx);
     } else if (rl == 16) {
       L.p = lane & 15u, L.row = lane >> 4;
-      rows_body<MODE, 16, KSM, SM, CHM, VAR, SEG, MIDW == 2 ? 2 : 1, true, MIDW == 2 ? 0 : NSR4>(lds, L, cx);
+      constexpr bool two = C.mid == Mid::kTwoWords;
+      rows_body<MODE, 16, C.ksm, C.sm, C.chm, VAR, SEG, two ? 2 : 1, true, two ? 0 : C.nsr4>(lds, L, cx);
     } else if (RLF != 16) {
       L.p = lane & 31u, L.row = lane >> 5;
-      rows_body<MODE, 32, KSW, SW, CHW, VAR, SEG, 1, REDGE>(lds, L, cx);
+      rows_body<MODE, 32, C.ksw, C.sw, C.chw, VAR, SEG, 1, C.redge>(lds, L, cx);
     }
   }
   if (tl && lane == 0) tl[2] = __builtin_amdgcn_s_memrealtime();
 }
 
-hipError_t launch_rows(int var, CrcMode mode, const uint8_t* bytes, const uint64_t* off, uint64_t n, void* out,
-                       const void* images, int num_cus, hipStream_t stream, uint64_t* timeline = nullptr,
-                       const uint32_t* seg_len = nullptr, uint32_t cap = 0, uint32_t policy = kPolicyRows,
-                       uint32_t* stage_flag = nullptr, uint32_t epoch = 0) {
-  const bool verify = mode == CrcMode::kVerify;
-  if (n == 0) return hipSuccess;
-  // the slices of dispatch.hpp (the staged launch uses the same): at least
-  // one 16-lane row set per wave
-  const SlicePlan pl = slice_plan(n, num_cus);
+// What a rows launch works on.  seg_len: segment mode (off holds the frames'
+// starts); cap: kAppend's slot capacity; policy, stage_flag, epoch: the plain
+// entries' pairing with the staged launch (dispatch.hpp).
+struct RowsArgs {
+  const uint8_t* bytes;
+  const uint64_t* off;
+  uint64_t n;
+  void* out;
+  const void* images;
+  int num_cus;
+  hipStream_t stream;
+  uint64_t* timeline = nullptr;
+  const uint32_t* seg_len = nullptr;
+  uint32_t cap = 0;
+  uint32_t policy = kPolicyRows;
+  uint32_t* stage_flag = nullptr;
+  uint32_t epoch = 0;
+};
+
+// One instance over the slices of dispatch.hpp (the staged launch uses the
+// same): at least one 16-lane row set per wave.
+template <RowsCfg C>
+void launch_cfg(const RowsArgs& a) {
+  const SlicePlan pl = slice_plan(a.n, a.num_cus);
   static_assert(kWavesPerBlock == 16, "slice_plan's slices are whole 16-wave sets");
-  const uint64_t grid = pl.grid;
-  const uint64_t fpw = pl.per / kWavesPerBlock;
-  const uint4* img = static_cast<const uint4*>(images);
-  const dim3 g((unsigned)grid), b(kBlockThreads);
-#define LNX_LAUNCH(M, ...) \
-  hipLaunchKernelGGL((crc32_rows_kernel<M, __VA_ARGS__>), g, b, 0, stream, bytes, off, n, fpw, img, out, \
-                     timeline, seg_len, cap, policy, stage_flag, epoch)
-  if (seg_len) {  // segment mode (lnx_crc32_segments, the TX FCS append, the receive ring)
-    // (every lean-row step non-temporal, EP = 0, was measured no faster for
-    // ring slots and is not built: profiles/r2s2r_segment_ep_rejected.txt)
-    if (verify)
-      LNX_LAUNCH(CrcMode::kVerify, 0, 0, 24, 1, 12, 2, 4, 16, true);
+  hipLaunchKernelGGL((crc32_rows_kernel<C>), dim3((unsigned)pl.grid), dim3(kBlockThreads), 0, a.stream, a.bytes, a.off,
+                     a.n, pl.per / kWavesPerBlock, static_cast<const uint4*>(a.images), a.out, a.timeline, a.seg_len,
+                     a.cap, a.policy, a.stage_flag, a.epoch);
+}
+
 #ifdef LNX_RESEARCH
-    else if (mode == CrcMode::kAppend && var == 4)  // profiling: FCS stored at once, no hold
-      LNX_LAUNCH(CrcMode::kAppend, 4, 0, 24, 1, 12, 2, 4, 16, true);
-    else if (mode == CrcMode::kAppend && var == 7)  // profiling: the FCS written with its 64-byte sector
-      LNX_LAUNCH(CrcMode::kAppend, 7, 0, 24, 1, 12, 2, 4, 16, true);
+#include "research/crc_variants.inc"
 #endif
-    else if (mode == CrcMode::kAppend)
-      LNX_LAUNCH(CrcMode::kAppend, 0, 0, 24, 1, 12, 2, 4, 16, true);
+
+// var: a research id (research/crc_variants.inc); the product library ignores it.
+hipError_t launch_rows([[maybe_unused]] int var, CrcMode mode, const RowsArgs& a) {
+  if (a.n == 0) return hipSuccess;
+  if (a.seg_len) {  // segment mode (lnx_crc32_segments, the TX FCS append, the receive ring)
+    // (every lean-row step non-temporal, lep = 0, was measured no faster for
+    // ring slots and is not built: profiles/r2s2r_segment_ep_rejected.txt)
+    if (mode == CrcMode::kVerify)
+      launch_cfg<in_mode(kRowsSegments, CrcMode::kVerify)>(a);
+    else if (mode == CrcMode::kCrc)
+      launch_cfg<in_mode(kRowsSegments, CrcMode::kCrc)>(a);
+#ifdef LNX_RESEARCH
+    else if (launch_append_variant(var, a)) {}
+#endif
     else
-      LNX_LAUNCH(CrcMode::kCrc, 0, 0, 24, 1, 12, 2, 4, 16, true);
-  } else if (verify) {
-    LNX_LAUNCH(CrcMode::kVerify, 0);
+      launch_cfg<in_mode(kRowsSegments, CrcMode::kAppend)>(a);
+  } else if (mode == CrcMode::kVerify) {
+    launch_cfg<in_mode(kRowsOffsets, CrcMode::kVerify)>(a);
+#ifdef LNX_RESEARCH
+  } else if (launch_offsets_variant(var, a)) {
+#endif
   } else {
-#ifndef LNX_RESEARCH
-    (void)var;
-    LNX_LAUNCH(CrcMode::kCrc, 0);
-#else
-    // profiling variants (tools/prof/variants.py).  Arguments:
-    // VAR, forced row width (0 = per workgroup), KSW, SW, KS4, S4, CHW, CH4,
-    // SEG, MIDW, KSM, SM, CHM
-#define LNX_16(W, KS_, S_, CH_) LNX_LAUNCH(CrcMode::kCrc, 0, 16, 24, 1, 12, 2, 4, 16, false, W, KS_, S_, CH_)
-    switch (var) {
-      case 1: LNX_LAUNCH(CrcMode::kCrc, 1); break;  // loads + bookkeeping only
-      case 2: LNX_LAUNCH(CrcMode::kCrc, 2); break;  // lookups + bookkeeping only
-      case 3: LNX_LAUNCH(CrcMode::kCrc, 3); break;  // bounds window loaded by all 64 lanes
-      case 5: LNX_LAUNCH(CrcMode::kCrc, 5); break;  // clock-window flushes for 4-lane rows too
-      // 10-16: forced 32-lane rows (KSW, SW, CHW vary)
-      case 10: LNX_LAUNCH(CrcMode::kCrc, 0, 32, 13, 1, 12, 2, 4, 16); break;  // one 13-line item per 1500 B
-      case 11: LNX_LAUNCH(CrcMode::kCrc, 0, 32, 13, 2, 12, 2, 4, 16); break;  // two-slot ring
-      case 12: LNX_LAUNCH(CrcMode::kCrc, 0, 32, 14, 1, 12, 2, 4, 16); break;
-      case 13: LNX_LAUNCH(CrcMode::kCrc, 0, 32, 13, 1, 12, 2, 2, 16); break;  // 2-frame chunks
-      case 14: LNX_LAUNCH(CrcMode::kCrc, 0, 32, 13, 1, 12, 2, 8, 16); break;  // 8-frame chunks
-      case 15: LNX_LAUNCH(CrcMode::kCrc, 0, 32, 24, 1, 12, 2, 4, 16); break;  // 24-line items
-      case 16: LNX_LAUNCH(CrcMode::kCrc, 0, 32, 18, 1, 12, 2, 4, 16); break;
-      // forced 16-lane rows: one word per lane (17, 21), two words per lane (18, 19, 28, 29, 40-42)
-      case 17: LNX_16(1, 24, 1, 4); break;  // round-1 product
-      case 21: LNX_16(1, 12, 3, 4); break;
-      case 18: LNX_16(2, 13, 1, 4); break;  // one 13-line item per 1500 B
-      case 19: LNX_16(2, 13, 2, 4); break;  // two-slot ring
-      case 28: LNX_16(2, 14, 1, 4); break;
-      case 29: LNX_16(2, 24, 1, 4); break;  // 24-line items
-      case 43: LNX_16(2, 32, 1, 4); break;  // 32-line items
-      case 44: LNX_16(2, 18, 1, 4); break;
-      case 40: LNX_16(2, 13, 1, 8); break;  // 8-frame chunks
-      case 41: LNX_16(2, 12, 2, 4); break;
-      case 42: LNX_16(2, 13, 1, 16); break;
-      // forced lean line rows (lines_body): KSL 13 / 14 / 12, loads only, math only
-#define LNX_LEAN(V, KSL_) LNX_LAUNCH(CrcMode::kCrc, V, 16, 24, 1, 12, 2, 4, 16, false, 3, 24, 1, 4, KSL_)
-      case 50: LNX_LEAN(0, 13); break;
-      case 51: LNX_LEAN(0, 14); break;
-      case 52: LNX_LEAN(0, 12); break;
-      case 53: LNX_LEAN(1, 13); break;
-      case 54: LNX_LEAN(2, 13); break;
-      // forced lean rows on 32 lanes x one word (KSL 13), loads only, math only
-      case 70: LNX_LAUNCH(CrcMode::kCrc, 0, 16, 24, 1, 12, 2, 4, 16, false, 3, 24, 1, 4, 13, 1); break;
-      case 71: LNX_LAUNCH(CrcMode::kCrc, 1, 16, 24, 1, 12, 2, 4, 16, false, 3, 24, 1, 4, 13, 1); break;
-      case 72: LNX_LAUNCH(CrcMode::kCrc, 2, 16, 24, 1, 12, 2, 4, 16, false, 3, 24, 1, 4, 13, 1); break;
-      // product dispatch with one-word 16-lane rows instead of lean rows (the r1f product)
-      case 56: LNX_LAUNCH(CrcMode::kCrc, 0, 0, 24, 1, 12, 2, 4, 16, false, 1); break;
-      // the product dispatch with the r1 lean rows (junk word reloaded, its U-image taken out), and its loads only
-      case 57: LNX_LAUNCH(CrcMode::kCrc, 0, 0, 24, 1, 12, 2, 4, 16, false, 4, 24, 1, 4, 13, 2, false); break;
-      case 58: LNX_LAUNCH(CrcMode::kCrc, 1, 0, 24, 1, 12, 2, 4, 16, false, 4, 24, 1, 4, 13, 2, false); break;
-      // lean rows by the cache policy of their step loads (lines_body EP): all nt (the r2b product) and
-      // its loads only, the first step at the default policy, every step at the default policy
-      case 90: LNX_LAUNCH(CrcMode::kCrc, 0, 0, 24, 1, 12, 2, 4, 16, false, 4, 24, 1, 4, 13, 2, true, 0); break;
-      case 91: LNX_LAUNCH(CrcMode::kCrc, 1, 0, 24, 1, 12, 2, 4, 16, false, 4, 24, 1, 4, 13, 2, true, 0); break;
-      case 92: LNX_LAUNCH(CrcMode::kCrc, 0, 0, 24, 1, 12, 2, 4, 16, false, 4, 24, 1, 4, 13, 2, true, 2); break;
-      case 93: LNX_LAUNCH(CrcMode::kCrc, 0, 0, 24, 1, 12, 2, 4, 16, false, 4, 24, 1, 4, 13, 2, true, 3); break;
-      // the product dispatch with 32-lane line rows all nt (the r1 form)
-      case 97: LNX_LAUNCH(CrcMode::kCrc, 0, 0, 24, 1, 16, 2, 4, 32, false, 4, 24, 1, 4, 13, 2, true, 1, false); break;
-#undef LNX_LEAN
-      // forced 4-lane rows
-      case 22: LNX_LAUNCH(CrcMode::kCrc, 0, 4); break;
-      case 23: LNX_LAUNCH(CrcMode::kCrc, 0, 4, 24, 1, 8, 3, 4, 64); break;
-      case 24: LNX_LAUNCH(CrcMode::kCrc, 0, 4, 24, 1, 12, 2, 4, 32); break;
-      case 25: LNX_LAUNCH(CrcMode::kCrc, 0, 4, 24, 1, 6, 3, 4, 64); break;
-      case 60: LNX_LAUNCH(CrcMode::kCrc, 0, 4, 24, 1, 16, 2, 4, 16); break;  // longer 4-lane items
-      case 61: LNX_LAUNCH(CrcMode::kCrc, 0, 4, 24, 1, 20, 1, 4, 16); break;
-      case 62: LNX_LAUNCH(CrcMode::kCrc, 0, 4, 24, 1, 12, 2, 4, 32); break;
-      case 63: LNX_LAUNCH(CrcMode::kCrc, 0, 4, 24, 1, 16, 2, 4, 32); break;
-      case 64: LNX_LAUNCH(CrcMode::kCrc, 0, 4, 24, 1, 12, 2, 4, 64); break;
-      case 65: LNX_LAUNCH(CrcMode::kCrc, 0, 4, 24, 1, 16, 2, 4, 64); break;
-      // narrow and one-word 16-lane rows by the runs their item loads (NSR4): 125 every step of
-      // the item (the r2 product: a short last item reads the next frames' bytes), 124 / 120 / 126
-      // runs of 1 / 2 / 6 steps (the product: 4; r2ze/r2zf Zipf 1.057 ms against 1.071 for 2, 1.077
-      // for every step, 1.056 for 6)
-      case 125: LNX_LAUNCH(CrcMode::kCrc, 0, 0, 24, 1, 16, 2, 4, 32, false, 4, 24, 1, 4, 13, 2, true, 1, true, 0); break;
-      case 120: LNX_LAUNCH(CrcMode::kCrc, 0, 0, 24, 1, 16, 2, 4, 32, false, 4, 24, 1, 4, 13, 2, true, 1, true, 2); break;
-      case 124: LNX_LAUNCH(CrcMode::kCrc, 0, 0, 24, 1, 16, 2, 4, 32, false, 4, 24, 1, 4, 13, 2, true, 1, true, 1); break;
-      case 126: LNX_LAUNCH(CrcMode::kCrc, 0, 0, 24, 1, 16, 2, 4, 32, false, 4, 24, 1, 4, 13, 2, true, 1, true, 6); break;
-      // four-word 4-lane rows (dwordx4: 64 contiguous bytes per row instruction) under the product
-      // dispatch: KS4 steps of 64 B, S4 slots, CH4-frame chunks, NSR4-step load runs
-#define LNX_W4(V, KS_, S_, CH_, NSR_) \
-  LNX_LAUNCH(CrcMode::kCrc, V, 0, 24, 1, KS_, S_, 4, CH_, false, 4, 24, 1, 4, 13, 2, true, 1, true, NSR_, 4)
-      case 130: LNX_W4(0, 4, 2, 32, 1); break;
-      case 135: LNX_W4(1, 4, 2, 32, 1); break;  // loads + bookkeeping only
-      case 136: LNX_W4(2, 4, 2, 32, 1); break;  // math + bookkeeping only
-      case 138: LNX_W4(0, 4, 2, 16, 1); break;
-      case 139: LNX_W4(0, 3, 2, 32, 1); break;
-      case 140: LNX_W4(0, 5, 2, 32, 1); break;
-#undef LNX_W4
-      // streaming rows (research/stream_rows.hpp) for the narrow rows' frames, under the product dispatch
-      case 150: LNX_LAUNCH(CrcMode::kCrc, 0, 0, 24, 1, 16, 2, 4, 32, false, 4, 24, 1, 4, 13, 2, true, 1, true, 4, 1, 1); break;
-      // its loads + chain only (no frame boundaries), loads only
-      case 151: LNX_LAUNCH(CrcMode::kCrc, 151, 0, 24, 1, 16, 2, 4, 32, false, 4, 24, 1, 4, 13, 2, true, 1, true, 4, 1, 1); break;
-      case 152: LNX_LAUNCH(CrcMode::kCrc, 152, 0, 24, 1, 16, 2, 4, 32, false, 4, 24, 1, 4, 13, 2, true, 1, true, 4, 1, 1); break;
-      // the same on 4-lane rows (64-byte row steps, at most one boundary per step): full, loads + chain, loads
-      case 153: LNX_LAUNCH(CrcMode::kCrc, 0, 0, 24, 1, 16, 2, 4, 32, false, 4, 24, 1, 4, 13, 2, true, 1, true, 4, 1, 2); break;
-      case 154: LNX_LAUNCH(CrcMode::kCrc, 151, 0, 24, 1, 16, 2, 4, 32, false, 4, 24, 1, 4, 13, 2, true, 1, true, 4, 1, 2); break;
-      case 155: LNX_LAUNCH(CrcMode::kCrc, 152, 0, 24, 1, 16, 2, 4, 32, false, 4, 24, 1, 4, 13, 2, true, 1, true, 4, 1, 2); break;
-      // lane streams (research/stream_lanes.hpp): full, loads only, loads + chain only
-      case 160: LNX_LAUNCH(CrcMode::kCrc, 0, 0, 24, 1, 16, 2, 4, 32, false, 4, 24, 1, 4, 13, 2, true, 1, true, 4, 1, 3); break;
-      case 161: LNX_LAUNCH(CrcMode::kCrc, 161, 0, 24, 1, 16, 2, 4, 32, false, 4, 24, 1, 4, 13, 2, true, 1, true, 4, 1, 3); break;
-      case 162: LNX_LAUNCH(CrcMode::kCrc, 162, 0, 24, 1, 16, 2, 4, 32, false, 4, 24, 1, 4, 13, 2, true, 1, true, 4, 1, 3); break;
-      case 164: LNX_LAUNCH(CrcMode::kCrc, 164, 0, 24, 1, 16, 2, 4, 32, false, 4, 24, 1, 4, 13, 2, true, 1, true, 4, 1, 3); break;  // reset in the fold
-      case 165: LNX_LAUNCH(CrcMode::kCrc, 165, 0, 24, 1, 16, 2, 4, 32, false, 4, 24, 1, 4, 13, 2, true, 1, true, 4, 1, 3); break;  // + offsets on even sets only
-      case 26: LNX_LAUNCH(CrcMode::kCrc, 1, 4); break;  // 4-lane rows, loads only
-      case 27: LNX_LAUNCH(CrcMode::kCrc, 2, 4); break;  // 4-lane rows, math only
-      default: LNX_LAUNCH(CrcMode::kCrc, 0); break;
-    }
-#undef LNX_16
-#endif  // LNX_RESEARCH
+    launch_cfg<kRowsOffsets>(a);
   }
-#undef LNX_LAUNCH
   return hipGetLastError();
 }
 
@@ -1994,8 +1905,9 @@ hipError_t launch_rows(int var, CrcMode mode, const uint8_t* bytes, const uint64
 hipError_t launch_crc32_frames(const uint8_t* bytes, const uint64_t* off, uint64_t n, void* out, bool verify,
                                const void* images, int num_cus, hipStream_t stream, uint32_t policy,
                                uint32_t* stage_flag, uint32_t epoch) {
-  return launch_rows(0, verify ? CrcMode::kVerify : CrcMode::kCrc, bytes, off, n, out, images, num_cus, stream,
-                     nullptr, nullptr, 0, policy, stage_flag, epoch);
+  return launch_rows(0, verify ? CrcMode::kVerify : CrcMode::kCrc,
+                     {.bytes = bytes, .off = off, .n = n, .out = out, .images = images, .num_cus = num_cus, .stream = stream,
+                      .policy = policy, .stage_flag = stage_flag, .epoch = epoch});
 }
 #ifdef LNX_RESEARCH
 hipError_t launch_crc32_variant(int var, const uint8_t* bytes, const uint64_t* off, uint64_t n, void* out,
@@ -2003,22 +1915,27 @@ hipError_t launch_crc32_variant(int var, const uint8_t* bytes, const uint64_t* o
   // 80 / 81: the product with 2 / 4 workgroups per CU over the launch (one is
   // resident at a time: the later ones go to the CUs that finish first)
   if (var == 80 || var == 81)
-    return launch_rows(0, CrcMode::kCrc, bytes, off, n, out, images, num_cus * (var == 80 ? 2 : 4), stream, nullptr);
-  return launch_rows(var, CrcMode::kCrc, bytes, off, n, out, images, num_cus, stream, timeline);
+    return launch_rows(0, CrcMode::kCrc, {.bytes = bytes, .off = off, .n = n, .out = out, .images = images,
+                                          .num_cus = num_cus * (var == 80 ? 2 : 4), .stream = stream});
+  return launch_rows(var, CrcMode::kCrc, {.bytes = bytes, .off = off, .n = n, .out = out, .images = images,
+                                          .num_cus = num_cus, .stream = stream, .timeline = timeline});
 }
 #endif
 hipError_t launch_crc32_segments(const uint8_t* bytes, const uint64_t* start, const uint32_t* len, uint64_t n,
                                  void* out, const void* images, int num_cus, hipStream_t stream) {
-  return launch_rows(0, CrcMode::kCrc, bytes, start, n, out, images, num_cus, stream, nullptr, len);
+  return launch_rows(0, CrcMode::kCrc, {.bytes = bytes, .off = start, .n = n, .out = out, .images = images,
+                                        .num_cus = num_cus, .stream = stream, .seg_len = len});
 }
 hipError_t launch_fcs_verify_segments(const uint8_t* bytes, const uint64_t* start, const uint32_t* len, uint64_t n,
                                       uint8_t* ok, const void* images, int num_cus, hipStream_t stream) {
-  return launch_rows(0, CrcMode::kVerify, bytes, start, n, ok, images, num_cus, stream, nullptr, len);
+  return launch_rows(0, CrcMode::kVerify, {.bytes = bytes, .off = start, .n = n, .out = ok, .images = images,
+                                           .num_cus = num_cus, .stream = stream, .seg_len = len});
 }
 // TX FCS append in place (kAppend, one launch): pad to 60, LE FCS, len += pad + 4, status.
 hipError_t launch_fcs_append(uint8_t* bytes, const uint64_t* start, uint32_t* len, uint64_t n, uint32_t capacity,
                              uint8_t* status, const void* images, int num_cus, hipStream_t stream, int var) {
-  return launch_rows(var, CrcMode::kAppend, bytes, start, n, status, images, num_cus, stream, nullptr, len, capacity);
+  return launch_rows(var, CrcMode::kAppend, {.bytes = bytes, .off = start, .n = n, .out = status, .images = images,
+                                             .num_cus = num_cus, .stream = stream, .seg_len = len, .cap = capacity});
 }
 #ifdef LNX_RESEARCH
 // TX FCS append, second launch (lnx__fcs_append_variant 200): frame i's CRC, taken
@@ -2070,10 +1987,7 @@ hipError_t launch_fcs_scatter(uint8_t* bytes, const uint64_t* start, uint32_t* l
 
 // Waves of a launch (sizes the timeline buffer: 3 uint64 per wave).
 uint64_t crc32_launch_waves(uint64_t n, int num_cus) {
-  const uint64_t per_block = (uint64_t)kWavesPerBlock * 4;
-  uint64_t grid = (n + per_block - 1) / per_block;
-  if (grid > (uint64_t)num_cus) grid = (uint64_t)num_cus;
-  return grid * kWavesPerBlock;
+  return n == 0 ? 0 : slice_plan(n, num_cus).grid * kWavesPerBlock;
 }
 
 }  // namespace lnx

@@ -107,6 +107,42 @@ namespace rs {
 hipError_t launch_crc32_stage_research(const uint8_t* bytes, const uint64_t* off, uint64_t n, void* out, bool verify,
                                        int fold, int waves, const void* image, int num_cus, hipStream_t stream,
                                        bool big_blocks = false);
+// lnx__crc32_variant's staged ids (all in stage_research.hip, the round-4
+// kernel; the product staged kernel with its round-5 dispatch is
+// lnx_crc32_batch_ex(LNX_BATCH_SHORT_FRAMES)).  id: the CRC form; id + 1 is
+// its FCS verify form when `verify` is set.
+struct StageVariant {
+  int id, fold, waves;
+  bool big_blocks, verify;
+};
+inline constexpr StageVariant kStageVariants[] = {
+    {300, 2, 8, false, true},    // the staged lane streams (stage_kernel.hip), slicing-by-2 fold
+    {302, 4, 8, false, true},    // the 16-column Z_4 fold
+    {304, 2, 10, false, true},   // 300 with 10 waves per workgroup instead of 8 (retired)
+    {306, 4, 10, false, true},   // 302 with 10 waves (retired)
+    {308, 4, 8, true, true},     // 302 with 766-frame blocks
+    {310, 8, 8, false, true},    // the slicing-by-8 fold
+    {312, 9, 8, false, true},    // the slicing-by-8 fold with the boundary correction deferred
+    {314, 10, 8, false, true},   // the slicing-by-8 fold with the boundary word patched per half
+    {316, 11, 8, false, true},   // 314 with each half folded as two chains of four units
+    {318, 12, 8, false, true},   // 314 with 190-frame blocks
+    {320, 13, 8, false, true},   // 314 with 254-frame blocks
+    {322, 14, 8, false, true},   // 314 with the next block's offsets loaded ahead
+    {324, 15, 8, false, true},   // 314 with 510-frame blocks
+    {326, 16, 8, false, true},   // 314 with 6 waves
+    // timing only (wrong results; round 5)
+    {328, 17, 8, false, false},  // 314 without the transpose writes
+    {330, 18, 8, false, false},  // 314 with a two-op stand-in for the lookups
+    {332, 19, 8, false, false},  // 314 without the ending frames' capture and Z_c
+    {334, 20, 8, false, false},  // 314 without the carries
+    {340, 21, 8, false, false},  // the ring's loads alone
+    {342, 22, 8, false, false},  // loads + the LDS transpose
+};
+constexpr const StageVariant* stage_variant(int id) {
+  for (const StageVariant& v : kStageVariants)
+    if (id == v.id || (v.verify && id == v.id + 1)) return &v;
+  return nullptr;
+}
 }
 // crc32_kernel.hip
 hipError_t launch_crc32_variant(int var, const uint8_t* bytes, const uint64_t* off, uint64_t n, void* out,

@@ -58,7 +58,7 @@ __device__ __forceinline__ void quad_swap(u32x4& a, u32x4& b, bool hi) {
   }
 }
 
-template <CrcMode MODE, int VAR, int D = 2>
+template <CrcMode MODE, Probe VAR, int D = 2>
 __device__ __forceinline__ void lanes_body(const char* lds, const Lanes& L, const WaveCtx& cx) {
   static_assert(MODE != CrcMode::kAppend, "offsets mode only");
   const uint32_t lane = L.lane, qi = lane & 3u;
@@ -111,14 +111,14 @@ __device__ __forceinline__ void lanes_body(const char* lds, const Lanes& L, cons
   // is read (and transposed) first, then refilled for the superstep D ahead.
   u32x4 w[D][4];
   u32x4 ob[D][2];
-  constexpr bool HALF = VAR == 165 && D == 2;  // offset requests on even sets only (4 fewer VMEM per 2 supersteps)
+  constexpr bool HALF = VAR == Probe::kLanesHalfOffsets && D == 2;  // offset requests on even sets only (4 fewer VMEM per 2 supersteps)
   auto issue = [&](int s, uint32_t Pn, bool req, uint32_t kreq) {
     const uint32_t vp = Pn <= Pend ? Pn : kOOB;  // this lane's run, D supersteps ahead
     const uint32_t a0 = dpp_mov<0x00>(vp) + 16u * qi, a1 = dpp_mov<0x55>(vp) + 16u * qi,
                    a2 = dpp_mov<0xAA>(vp) + 16u * qi, a3 = dpp_mov<0xFF>(vp) + 16u * qi;
     const uint32_t f0 = fa + kreq, f2 = fa + kreq + 2u;
     const uint32_t vo0 = req && f0 <= nfb ? f0 * 8u : kOOB, vo1 = req && f2 <= nfb ? f2 * 8u : kOOB;
-    if (HALF && (s & 1)) {  // VAR 165: offsets only on even sets
+    if (HALF && (s & 1)) {  // kLanesHalfOffsets: offsets only on even sets
       asm volatile(
           "s_nop 4\n\t"
           "buffer_load_dwordx4 %0, %4, %8, 0 offen" LNX_LD_POL "\n\t"
@@ -174,7 +174,7 @@ __device__ __forceinline__ void lanes_body(const char* lds, const Lanes& L, cons
     }
     return e;
   };
-  // ---- VAR 164: the reset as a select inside the fold.  A
+  // ---- kLanesFoldReset: the reset as a select inside the fold.  A
   // frame starting at byte c of dword k makes the chain value there
   // y = (~w_k & hm) ^ K_c (hm = ~0 << 8c, K_c = Z_{-c}(the top c bytes of ~0)),
   // so Z4(y) is the new frame's state after the dword; only the ending
@@ -339,10 +339,10 @@ __device__ __forceinline__ void lanes_body(const char* lds, const Lanes& L, cons
       const bool req = !hasB && !reqd && kb + 4u <= m && !(HALF && (s & 1));
       issue(s, P + 64u * D, req, kb + 4u);
       if (req) reqd = true, reqs = (uint32_t)s;
-      if constexpr (VAR == 161) {  // profiling: loads only
+      if constexpr (VAR == Probe::kLanesLoads) {  // profiling: loads only
 #pragma unroll
         for (int i = 0; i < 4; ++i) r ^= Xs[i][0] ^ Xs[i][1] ^ Xs[i][2] ^ Xs[i][3];
-      } else if constexpr (VAR == 164 || VAR == 165) {
+      } else if constexpr (VAR == Probe::kLanesFoldReset || VAR == Probe::kLanesHalfOffsets) {
         const uint32_t r0 = r, rp1 = x - P, kev = rp1 >> 2, c1 = rp1 & 3u;  // kev >= 16: no boundary here
         const uint32_t hm1 = 0xFFFFFFFFu << (8u * c1);
         const uint32_t Kc = c1 == 1u ? kK1 : c1 == 2u ? kK2 : c1 == 3u ? kK3 : 0u;
@@ -401,7 +401,7 @@ __device__ __forceinline__ void lanes_body(const char* lds, const Lanes& L, cons
         }
         const uint32_t rn = u_step(lds, y, bu0, bu1);
         uint32_t fix = 0, Sp = 0, xp = 0;
-        if constexpr (VAR != 162) {  // 162 (profiling): loads + chain only
+        if constexpr (VAR != Probe::kLanesChain) {  // 162 (profiling): loads + chain only
           if (wave_any(x - P < 64u)) {
             pass(false, ye, we, r0, Xs, fix, Sp, xp);
             while (wave_any(x - P < 64u)) pass(true, ye, we, r0, Xs, fix, Sp, xp);
@@ -417,7 +417,7 @@ __device__ __forceinline__ void lanes_body(const char* lds, const Lanes& L, cons
     }
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  if constexpr (VAR == 161 || VAR == 162) {  // keep the fold live
+  if constexpr (VAR == Probe::kLanesLoads || VAR == Probe::kLanesChain) {  // keep the fold live
     if (r == 0x9E3779B9u) __builtin_amdgcn_raw_buffer_store_b32(r, out_rsrc, 0, 0, 0);
   }
 }

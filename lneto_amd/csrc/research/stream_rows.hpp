@@ -65,7 +65,7 @@ __device__ __forceinline__ uint32_t rowx(uint32_t v) {
 // 4: a 64-byte half line, the stream64 image).  With 4-lane rows a frame of
 // at least 64 bytes ends at most once per row step, so a step takes one
 // boundary pass where 8-lane rows take up to two.
-template <CrcMode MODE, int VAR, int RLS = 8, int D = 4>
+template <CrcMode MODE, Probe VAR, int RLS = 8, int D = 4>
 __device__ __forceinline__ void stream_body(const char* lds, const Lanes& L, const WaveCtx& cx) {
   static_assert(MODE != CrcMode::kAppend, "offsets mode only");
   static_assert(RLS == 8 || RLS == 4, "row width");
@@ -268,7 +268,7 @@ __device__ __forceinline__ void stream_body(const char* lds, const Lanes& L, con
       if (req) reqd = true, reqs = (uint32_t)sn;
       // the fold
       uint32_t ra;
-      if constexpr (VAR == 152) {  // profiling: loads only
+      if constexpr (VAR == Probe::kStreamLoads) {  // profiling: loads only
         ra = r ^ wv[0] ^ wv[1] ^ wv[2] ^ wv[3];
       } else {
         uint32_t y0 = r ^ wv[0];
@@ -276,7 +276,7 @@ __device__ __forceinline__ void stream_body(const char* lds, const Lanes& L, con
         uint32_t y2 = u_step_xor(lds, y1, wv[2], bu0, bu1);
         uint32_t y3 = u_step_xor(lds, y2, wv[3], bu0, bu1);
         ra = z116(lds, y3);
-        if constexpr (VAR != 151) event_loop(wv, y0, y1, y2, y3, ra);  // 151 (profiling): loads + chain only
+        if constexpr (VAR != Probe::kStreamChain) event_loop(wv, y0, y1, y2, y3, ra);  // 151 (profiling): loads + chain only
       }
       r = ra;
       Lr += SB;
@@ -287,7 +287,7 @@ __device__ __forceinline__ void stream_body(const char* lds, const Lanes& L, con
     }
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  if constexpr (VAR == 151 || VAR == 152) {  // keep the fold live
+  if constexpr (VAR == Probe::kStreamChain || VAR == Probe::kStreamLoads) {  // keep the fold live
     if (r == 0x9E3779B9u) store_held();
   }
 }

@@ -112,15 +112,17 @@ def _kernels(path):
 
 def test_product_library_holds_only_product_kernels():
     """The product .so carries exactly the shipped kernel instances: every
-    crc32_rows_kernel with VAR = 0 and no streaming form (STR = 0), one instance
+    crc32_rows_kernel with no probe and no streaming form (RowsCfg::probe and
+    ::stream 0), one instance
     each of sum16 / search / ring, ingress verify + TX generate; the research
     variants live in liblneto_amd_research.so only."""
     ks = _kernels(L.LIB_PATH)
     rows = [k for k in ks if "crc32_rows_kernel" in k]
     assert len(rows) == 5, rows  # offsets crc / verify, segments crc / verify / append
     for k in rows:
-        assert re.search(r"CrcModeE\dELi0E", k), k          # VAR = 0
-        assert re.search(r"ELi0EEEvPKh", k), k              # STR = 0
+        # RowsCfg's first members (rows_cfg.hpp), in the struct argument's mangling: mode, probe, stream, width
+        assert re.search(r"RowsCfgELNS_7CrcModeE\dELNS_5ProbeE0ELNS_6StreamE", k), k   # Probe::kProduct
+        assert re.search(r"ELNS_5ProbeE\d+ELNS_6StreamE0ELNS_5WidthE", k), k           # Stream::kNone
     others = sorted(re.sub(r"^_ZN3lnx\d+(\w+?kernel).*$", r"\1", k) for k in ks if k not in rows)
     # ingress: filtered / unfiltered verdicts, TX generate; rx_verify: (FCS / none) x (filter / none) x
     # (HBM / host memory); tx_finish: (FCS / none) x (checksum / none) x (HBM / host memory)

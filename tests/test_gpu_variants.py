@@ -4,7 +4,8 @@ workgroup, is bit-exact against the oracle.
 The product dispatch (lnx_crc32_batch) chooses the row width per workgroup from
 its frames' mean length, so a given test batch exercises only some of the
 compiled configurations.  The profiling entry point lnx__crc32_variant forces
-one configuration for the whole launch (ids in crc32_kernel.hip launch_rows).
+one configuration for the whole launch (ids in lneto_amd/csrc/research/crc_variants.inc,
+each a product configuration of rows_cfg.hpp with some fields changed).
 """
 import ctypes
 
@@ -17,13 +18,14 @@ from oracle import oracle as O
 
 pytestmark = pytest.mark.gpu
 
+# (research/crc_variants.inc holds the table; (KS, S): RowsCfg ksw / ksm / ks4 and sw / sm / s4)
 # 10..16: forced 32-lane rows (line-aligned windows, nt loads), (KS, S) = (13, 1), (13, 2),
 #   (14, 1), (13, 1) with 2- and 8-frame chunks, (24, 1), (18, 1);
 # 17/21: forced one-word 16-lane rows, (KS, S) = (24, 1), (12, 3);
 # 18/19/28/29/40/41/42: forced two-word 16-lane rows (line windows, dwordx2 nt loads),
 #   (13, 1), (13, 2), (14, 1), (24, 1), (13, 1) with 8- and 16-frame chunks, (12, 2);
 # 22..25, 60, 63: forced 4-lane rows (16, 2) with 32-frame chunks, (8, 3), (12, 2), (6, 3), (16, 2) with 16, (16, 2) with 32;
-# 50..52: forced lean line rows (lines_body), KSL = 13, 14, 12;
+# 50..52: forced lean line rows (lines_body), ksl = 13, 14, 12;
 # 56: the product dispatch with one-word 16-lane rows instead of lean rows;
 # 70: forced lean rows on 32 lanes x one word;
 # 125: the product dispatch with 4-lane and one-word 16-lane rows loading every step of an item (r2),

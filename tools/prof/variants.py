@@ -1,6 +1,6 @@
 """Time the CRC kernel's profiling variants on one workload.
 0 = product kernel, 1 = loads + bookkeeping only, 2 = lookups + bookkeeping only
-(other numbers: crc32_kernel.hip launch_rows).  The GPU is warmed for ~0.5 s
+(other numbers: lneto_amd/csrc/research/crc_variants.inc).  The GPU is warmed for ~0.5 s
 first (the first few hundred microseconds of launches run at lower clocks),
 then the variants are timed round-robin REPS times and the median is printed,
 so box drift hits every variant alike.
