@@ -630,6 +630,78 @@ int lnx_rx_rst_reply_batch(const uint8_t* d_bytes, const uint64_t* d_off, uint64
 int lnx_tcp_rst_frames_batch(const lnx_rst_cfg* cfg, const lnx_tcp_rst* d_entry, uint64_t n, const uint16_t* d_ip_id,
                              uint8_t* d_reply, void* stream);
 
+/* Echo replies for ICMPv4 echo requests: the other frame the
+ * stack sends back on its own.  icmpv4.Client.Demux stores an echo request's
+ * identifier, sequence number, source address and data
+ * (ipv4/icmpv4/client.go:111-132) and the next Encapsulate sends them back as an
+ * echo reply (client.go:162-176, 209-218).  A frame queues an entry when its
+ * delivery record has verdict 0 and handler LNX_H_IP4 + 1, the record's l4_off
+ * and ip_end satisfy 34 <= l4_off, l4_off + 9 <= ip_end <= len and
+ * ip_end - l4_off - 8 <= 65507, its ICMP type is 8 and the version nibble of its
+ * byte 14 is 4 (for another nibble under a stale record the reference would
+ * answer to 0.0.0.0: deliberately not restated).  CONTRACT: the records must come
+ * from a receive call with LNX_VERIFY_ICMP (lnx_rx_verify_deliver_batch, or
+ * lnx_rx_deliver_batch behind such a check): the request's ICMP checksum
+ * (client.go:99-102) is the verdict's business, as the FCS is, and the entry does
+ * not check it again.  The entry becomes the frame StackEthernet.Encapsulate,
+ * encapsulate4 and Client.Encapsulate write (internet/stack-ethernet.go:170-217,
+ * internet/stack-ip4.go:178-231): 42 header bytes (IHL 5, the IP ID, don't
+ * fragment, TTL 64, type 0, code 0, the request's id and seq, both checksums
+ * taken fresh), the request's data, zero padding to 60 bytes and, with
+ * LNX_TX_FCS, its LE FCS.  NOT restated: incomingEcho's capacity and
+ * ErrExhausted, the response ring's size, one reply per Encapsulate call and the
+ * MTU clip of the carrier buffer; the batch entry answers every queueing frame,
+ * in arrival order, up to the caller's capacities, and reports what it left out.
+ * lnx_rst_cfg is the stack's side of this reply too. */
+typedef struct lnx_icmp_echo {
+  uint8_t remote_addr[4];
+  uint16_t id, seq;
+  uint32_t data_off, data_len;  /* the data is frame[data_off : data_off + data_len], 1 <= data_len <= 65507 */
+} lnx_icmp_echo;
+/* The entry frame[0 : len] (FCS stripped) queues under its record: 1 with *out
+ * written, 0 for none (*out untouched), LNX_EINVAL for a NULL rec or out or a
+ * NULL frame with len > 0.  Only len bounds what is read. */
+int lnx_rx_echo_entry(const uint8_t* frame, size_t len, const lnx_rx_delivery* rec, lnx_icmp_echo* out);
+/* The reply of one entry with IP ID ip_id and the data data[0 : e->data_len]
+ * (frame + e->data_off; it must not overlap out): exactly *len bytes of out are
+ * written, *len = max(60, 42 + data_len), plus 4 with LNX_TX_FCS.  Returns
+ * LNX_OK; 6 (ErrShortBuffer, as lnx_fcs_append) with nothing written when
+ * out_cap is smaller than that; LNX_EINVAL for a NULL pointer, an unknown bit in
+ * cfg->flags or a data_len outside 1..65507. */
+int lnx_icmp_echo_reply_frame(const lnx_rst_cfg* cfg, const lnx_icmp_echo* e, const uint8_t* data, uint16_t ip_id,
+                              uint8_t* out, uint32_t out_cap, uint32_t* len);
+/* The replies of a batch, chained behind lnx_rx_deliver_batch /
+ * lnx_rx_verify_deliver_batch on the same d_off (any order; an end below its
+ * start is an empty frame) and d_rec.  flags: LNX_RX_NO_FCS or 0 (frames carry
+ * their FCS).  Reply k answers the k-th queueing frame in index order and
+ * carries the IP ID d_ip_id[k].  With len_k its length (FCS included under
+ * LNX_TX_FCS) it occupies ceil(len_k / 64) whole 64-byte blocks of d_reply
+ * (64-byte aligned), starting at 64 x the sum of the earlier replies' blocks:
+ * d_start[k] is that byte offset and d_len[k] = len_k, the form
+ * lnx_fcs_verify_segments / lnx_tx_finish_batch take; d_src[k] is the index of
+ * the frame it answers; every byte of its blocks is written, zero past len_k.
+ * Reply k is written iff k < cap and its last block lies below cap_blocks (a
+ * prefix of the replies).  d_n[0..3] = {replies written, replies wanted, blocks
+ * written, blocks wanted}, the two block counts saturating at 2^32 - 1.  Nothing of d_reply,
+ * d_start, d_len or d_src at or past what was written is touched, and no ID
+ * past `written` is read.  d_ws: lnx_rx_echo_ws_bytes(n) bytes of the caller's
+ * device memory, 8-byte aligned.  Three launches (count, a one-workgroup scan,
+ * build), none waiting for another workgroup and no global atomics: every
+ * output is a pure function of the inputs.  n == 0: LNX_OK with d_n zeroed (a
+ * NULL d_n: nothing to do); cap == 0 or cap_blocks == 0: d_n alone is written.
+ * Alignment: d_reply 64 bytes; d_rec 16 (a record is read as one 16-byte load;
+ * the delivery entries write it so aligned); d_start and d_ws 8; d_len, d_src
+ * and d_n 4; d_ip_id 2.  LNX_EINVAL: n >= 2^32, a NULL pointer with work to do,
+ * an unknown flag bit on either flags word, a pointer that is not so aligned
+ * (NULL counts as aligned).  Asynchronous on `stream`; retains
+ * nothing, never synchronises the device and uses none of the library's
+ * per-stream scratch. */
+uint64_t lnx_rx_echo_ws_bytes(uint64_t n);
+int lnx_rx_echo_reply_batch(const uint8_t* d_bytes, const uint64_t* d_off, uint64_t n, uint32_t flags,
+                            const lnx_rx_delivery* d_rec, const lnx_rst_cfg* cfg, const uint16_t* d_ip_id,
+                            uint64_t cap, uint64_t cap_blocks, uint8_t* d_reply, uint64_t* d_start,
+                            uint32_t* d_len, uint32_t* d_src, uint32_t* d_n, void* d_ws, void* stream);
+
 /* pcap's checksum re-verification over a batch: d_status[i] =
  * lnx_pcap_checksums(d_bytes[d_off[i] : d_off[i+1]]) for every Ethernet frame
  * (FCS stripped; an end offset below its start is an empty frame).  Four

@@ -29,6 +29,7 @@ __all__ = [
     "H_ETH", "H_IP4", "H_IP6", "H_TCP", "H_UDP", "H_COUNT", "H_NONE", "DLV_RST", "DLV_IP6", "DLV_FCS",
     "RstCfg", "TcpRst", "TX_FCS", "TCP_RST", "TCP_ACK", "ip4_id_chain", "rx_rst_entry", "tcp_rst_frame",
     "rx_rst_ws_bytes", "rx_rst_reply_batch", "tcp_rst_frames_batch",
+    "IcmpEcho", "rx_echo_entry", "icmp_echo_reply_frame", "rx_echo_ws_bytes", "rx_echo_reply_batch",
 ]
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -161,7 +162,29 @@ class TcpRst(ctypes.Structure):
         return e
 
 
+class IcmpEcho(ctypes.Structure):
+    """lnx_icmp_echo (include/lneto_amd.h): what icmpv4.Client.Demux keeps of an echo
+    request (ipv4/icmpv4/client.go:128-132), the data as a range of the frame."""
+    _fields_ = [("remote_addr", ctypes.c_uint8 * 4), ("id", ctypes.c_uint16), ("seq", ctypes.c_uint16),
+                ("data_off", ctypes.c_uint32), ("data_len", ctypes.c_uint32)]
+
+    @classmethod
+    def make(cls, remote_addr: bytes, id: int, seq: int, data_off: int, data_len: int) -> "IcmpEcho":
+        if len(remote_addr) != 4:
+            raise LnetoError("IcmpEcho: remote_addr 4 bytes")
+        e = cls()
+        e.remote_addr[:] = list(remote_addr)
+        e.id, e.seq = id & 0xFFFF, seq & 0xFFFF
+        e.data_off, e.data_len = data_off, data_len
+        return e
+
+
 _sig = {
+    "lnx_rx_echo_entry": (ctypes.c_int, [_vp, ctypes.c_size_t, _vp, _vp]),
+    "lnx_icmp_echo_reply_frame": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_uint16, _vp, ctypes.c_uint32, _vp]),
+    "lnx_rx_echo_ws_bytes": (ctypes.c_uint64, [ctypes.c_uint64]),
+    "lnx_rx_echo_reply_batch": (ctypes.c_int, [_vp, _vp, ctypes.c_uint64, ctypes.c_uint32, _vp, _vp, _vp, ctypes.c_uint64,
+                                               ctypes.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lnx_ip4_id_chain": (None, [ctypes.c_uint8, ctypes.c_uint16, ctypes.c_uint64, _vp]),
     "lnx_rx_rst_entry": (ctypes.c_int, [_vp, ctypes.c_size_t, _vp, _vp]),
     "lnx_tcp_rst_frame": (ctypes.c_int, [_vp, _vp, ctypes.c_uint16, _vp, _vp]),
@@ -830,14 +853,7 @@ def _rst_entry_dict(e: TcpRst) -> dict:
 def rx_rst_entry(frame: bytes, rec) -> dict | None:
     """The RST entry ONE frame (FCS stripped) queues under its delivery record
     (lnx_rx_rst_entry), None for none.  rec: rx_deliver's dict, or the 16 record bytes."""
-    if isinstance(rec, dict):
-        raw = (rec["ip_end"].to_bytes(4, "little") + b"".join(rec[k].to_bytes(2, "little") for k in
-               ("handler", "l4_off", "src_port", "dst_port")) + bytes([rec["verdict"], rec["flags"]]) +
-               rec.get("zero", 0).to_bytes(2, "little"))
-    else:
-        raw = bytes(rec)
-    if len(raw) != 16:
-        raise LnetoError("rx_rst_entry: a delivery record is 16 bytes")
+    raw = _record_bytes("rx_rst_entry", rec)
     buf = bytes(frame)
     e = TcpRst()
     rc = lib.lnx_rx_rst_entry(buf, len(buf), raw, ctypes.byref(e))
@@ -922,6 +938,114 @@ def tcp_rst_frames_batch(cfg: RstCfg, d_entry, ip_ids, out=None, stream=None):
             _check(lib.lnx_tcp_rst_frames_batch(ctypes.byref(cfg), d_entry.data_ptr(), n, ip_ids.data_ptr(),
                                                 reply.data_ptr(), s), what)
     return reply.view(-1)[:64 * n].view(n, 64)
+
+
+# ------------------------------------------------------- echo replies
+def _record_bytes(what: str, rec) -> bytes:
+    if isinstance(rec, dict):
+        raw = (rec["ip_end"].to_bytes(4, "little") + b"".join(rec[k].to_bytes(2, "little") for k in
+               ("handler", "l4_off", "src_port", "dst_port")) + bytes([rec["verdict"], rec["flags"]]) +
+               rec.get("zero", 0).to_bytes(2, "little"))
+    else:
+        raw = bytes(rec)
+    if len(raw) != 16:
+        raise LnetoError(f"{what}: a delivery record is 16 bytes")
+    return raw
+
+
+def rx_echo_entry(frame: bytes, rec) -> dict | None:
+    """The echo entry ONE frame (FCS stripped) queues under its delivery record
+    (lnx_rx_echo_entry), None for none.  rec: rx_deliver's dict, or the 16 record
+    bytes, from a receive check with VERIFY_ICMP."""
+    raw = _record_bytes("rx_echo_entry", rec)
+    buf = bytes(frame)
+    e = IcmpEcho()
+    rc = lib.lnx_rx_echo_entry(buf, len(buf), raw, ctypes.byref(e))
+    if rc < 0:
+        _check(rc, "lnx_rx_echo_entry")
+    if rc != 1:
+        return None
+    return dict(remote_addr=bytes(e.remote_addr), id=e.id, seq=e.seq, data_off=e.data_off, data_len=e.data_len)
+
+
+def icmp_echo_reply_frame(cfg: RstCfg, entry, data: bytes, ip_id: int, out_cap: int | None = None) -> bytes:
+    """The reply of one entry (an IcmpEcho, or a dict as rx_echo_entry gives) whose
+    data is ``data`` (frame[data_off : data_off + data_len]) with IP ID ip_id
+    (lnx_icmp_echo_reply_frame): max(60, 42 + data_len) bytes, 4 more with cfg's
+    fcs.  out_cap: the room offered (default: enough); too little raises with
+    the library's ErrShortBuffer (6)."""
+    e = entry if isinstance(entry, IcmpEcho) else IcmpEcho.make(**entry)
+    data = bytes(data)
+    if len(data) != e.data_len:
+        raise LnetoError("icmp_echo_reply_frame: data holds data_len bytes")
+    room = max(60, 42 + len(data)) + 4 if out_cap is None else int(out_cap)
+    out = (ctypes.c_uint8 * max(room, 1))()
+    n = ctypes.c_uint32(0)
+    rc = lib.lnx_icmp_echo_reply_frame(ctypes.byref(cfg), ctypes.byref(e), data, ip_id & 0xFFFF, out, room, ctypes.byref(n))
+    if rc == 6:
+        raise LnetoError("lnx_icmp_echo_reply_frame failed: short buffer (6)")
+    _check(rc, "lnx_icmp_echo_reply_frame")
+    return bytes(out[:n.value])
+
+
+def rx_echo_ws_bytes(n: int) -> int:
+    """Bytes of device workspace lnx_rx_echo_reply_batch needs for n frames."""
+    return lib.lnx_rx_echo_ws_bytes(n)
+
+
+def rx_echo_reply_batch(d_bytes, d_off, d_rec, cfg: RstCfg, ip_id: int | None = None, ip_ids=None, flags: int = 0,
+                        cap: int | None = None, cap_blocks: int | None = None, stream=None):
+    """The echo replies of a batch behind rx_deliver_batch / rx_verify_deliver_batch
+    (with VERIFY_ICMP) on the same d_off and records (lnx_rx_echo_reply_batch):
+    returns (reply, start, length, src, written, wanted).  reply is [cap_blocks,
+    64] uint8; reply k is reply.view(-1)[start[k] : start[k] + length[k]] (int64
+    start, int32 length: the form fcs_verify / tx_finish_batch take), in whole
+    64-byte blocks, zero past its length, and answers frame src[k] (int32);
+    entries at or past ``written`` are left as allocated.  ip_id: the stack's
+    ipID, from which the chain of ``cap`` IDs is computed on the host and
+    uploaded (ip4_id_chain; RST and echo replies draw from ONE chain, which the
+    caller splits); or ip_ids: an int16 device tensor of at least ``cap`` IDs.
+    cap defaults to the number of frames, cap_blocks to what the replies of
+    that many frames packed back to back in d_bytes can take.  flags:
+    RX_NO_FCS or 0.  Synchronises to return the two counts."""
+    import torch
+    what = "lnx_rx_echo_reply_batch"
+    b = _Batch(what, [("d_bytes", d_bytes, "u8"), ("d_off", d_off, "i64"), ("d_rec", d_rec, "u8"),
+                      ("ip_ids", ip_ids, "i16?")], stream)
+    n = d_off.numel() - 1
+    if n < 0:
+        raise LnetoError(f"{what}: d_off holds no offset")
+    _need_len(what, "d_rec", d_rec, 16 * n)
+    if (ip_id is None) == (ip_ids is None):
+        raise LnetoError(f"{what}: give ip_id or ip_ids")
+    cap = n if cap is None else int(cap)
+    if cap_blocks is None:   # a reply is at most 4 bytes longer than its request, and at least one block
+        cap_blocks = min(d_bytes.numel() // 64 + 2 * n, 1025 * cap)
+    cap_blocks = int(cap_blocks)
+    if ip_ids is None:
+        import numpy as np
+        ids = np.array(ip4_id_chain(cfg.ip4[0], ip_id, cap), dtype=np.uint16).view(np.int16)
+        ip_ids = torch.from_numpy(ids).to(b.device)
+    _need_len(what, "ip_ids", ip_ids, cap)
+    reply = torch.empty((cap_blocks, 64), dtype=torch.uint8, device=b.device)
+    start = torch.empty(cap, dtype=torch.int64, device=b.device)
+    length = torch.empty(cap, dtype=torch.int32, device=b.device)
+    src = torch.empty(cap, dtype=torch.int32, device=b.device)
+    d_n = torch.empty(4, dtype=torch.int32, device=b.device)  # (written by every call)
+    ws = torch.empty(rx_echo_ws_bytes(n), dtype=torch.uint8, device=b.device)
+    room = cap > 0 and cap_blocks > 0
+    with b as s:
+        _check(lib.lnx_rx_echo_reply_batch(d_bytes.data_ptr(), d_off.data_ptr(), n, flags, d_rec.data_ptr(),
+                                           ctypes.byref(cfg), ip_ids.data_ptr() if room else None, cap, cap_blocks,
+                                           reply.data_ptr() if room else None, start.data_ptr() if room else None,
+                                           length.data_ptr() if room else None, src.data_ptr() if room else None,
+                                           d_n.data_ptr(), ws.data_ptr(), s), what)
+        if stream is not None:
+            for t in (ws, ip_ids):
+                t.record_stream(stream)
+            stream.synchronize()
+        counts = d_n.cpu().numpy().view("uint32")
+    return reply, start, length, src, int(counts[0]), int(counts[1])
 
 
 PCAP_IP_HDR_BAD, PCAP_PROTO_BAD = 1, 2  # LNX_PCAP_IP_HDR_BAD, LNX_PCAP_PROTO_BAD

@@ -37,6 +37,7 @@ struct DeviceCtx {
   uint32_t* d_stage = nullptr;   // crc32_stage_kernel image
   uint32_t* d_rx = nullptr;      // rx_verify_kernel image
   uint32_t* d_rst = nullptr;     // rst_reply_kernel image
+  uint32_t* d_echo = nullptr;    // echo_reply_kernel image
   // Per stream: the staged kernel's giant-slice slots (stage_kernel.hip
   // giant_pieces; zero between launches) and the gate words of the two-launch
   // entries.  Launches on one stream run in order, so each stream owns one
@@ -92,11 +93,13 @@ int init_ctx(DeviceCtx& c, int dev) {
     (void)hipFree(c.d_stage);
     (void)hipFree(c.d_rx);
     (void)hipFree(c.d_rst);
+    (void)hipFree(c.d_echo);
     c.d_image = nullptr;
     c.d_search = nullptr;
     c.d_stage = nullptr;
     c.d_rx = nullptr;
     c.d_rst = nullptr;
+    c.d_echo = nullptr;
     return hip_fail(err, what);
   };
   const hipError_t err = hipDeviceGetAttribute(&c.num_cus, hipDeviceAttributeMultiprocessorCount, dev);
@@ -113,6 +116,7 @@ int init_ctx(DeviceCtx& c, int dev) {
   if (st == LNX_OK) st = upload(&c.d_stage, build_stage_image(), "stage image");
   if (st == LNX_OK) st = upload(&c.d_rx, build_rx_image(), "rx image");
   if (st == LNX_OK) st = upload(&c.d_rst, build_rst_image(), "rst image");
+  if (st == LNX_OK) st = upload(&c.d_echo, build_echo_image(), "echo image");
   return st;
 }
 
@@ -706,6 +710,39 @@ int lnx_tcp_rst_frames_batch(const lnx_rst_cfg* cfg, const lnx_tcp_rst* d_entry,
   if (st != LNX_OK) return st;
   const hipError_t e = lnxr::launch_rst_frames(*cfg, d_entry, n, d_ip_id, d_reply, c->d_rst, static_cast<hipStream_t>(stream));
   if (e != hipSuccess) return hip_fail(e, "rst_frames_kernel launch");
+  return LNX_OK;
+}
+
+uint64_t lnx_rx_echo_ws_bytes(uint64_t n) { return lnxe::echo_ws_bytes(n); }
+
+// Echo replies behind the delivery records (echo_kernel.hip).
+// The workspace is the caller's, as in the delivery entries; the device context
+// gives the table image only.
+int lnx_rx_echo_reply_batch(const uint8_t* d_bytes, const uint64_t* d_off, uint64_t n, uint32_t flags,
+                            const lnx_rx_delivery* d_rec, const lnx_rst_cfg* cfg, const uint16_t* d_ip_id,
+                            uint64_t cap, uint64_t cap_blocks, uint8_t* d_reply, uint64_t* d_start,
+                            uint32_t* d_len, uint32_t* d_src, uint32_t* d_n, void* d_ws, void* stream) {
+  if (flags & ~(uint32_t)LNX_RX_NO_FCS) return LNX_EINVAL;
+  if (cfg && (cfg->flags & ~(uint32_t)LNX_TX_FCS)) return LNX_EINVAL;
+  if (n >> 32) return LNX_EINVAL;
+  auto misaligned = [](const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; };
+  if (misaligned(d_reply, 64) || misaligned(d_rec, 16) || misaligned(d_start, 8) || misaligned(d_len, 4) ||
+      misaligned(d_src, 4) || misaligned(d_n, 4) || misaligned(d_ws, 8) || misaligned(d_ip_id, 2))
+    return LNX_EINVAL;
+  const hipStream_t hs = static_cast<hipStream_t>(stream);
+  if (n == 0) {
+    if (!d_n) return LNX_OK;
+    const hipError_t e = hipMemsetAsync(d_n, 0, 4 * sizeof(uint32_t), hs);
+    return e == hipSuccess ? LNX_OK : hip_fail(e, "hipMemsetAsync(d_n)");
+  }
+  if (!d_bytes || !d_off || !d_rec || !cfg || !d_n || !d_ws) return LNX_EINVAL;
+  if (cap > 0 && cap_blocks > 0 && (!d_ip_id || !d_reply || !d_start || !d_len || !d_src)) return LNX_EINVAL;
+  DeviceCtx* c = nullptr;
+  const int st = get_ctx(&c);
+  if (st != LNX_OK) return st;
+  const hipError_t e = lnxe::launch_echo_reply(d_bytes, d_off, n, (flags & LNX_RX_NO_FCS) ? 0u : 4u, d_rec, *cfg, d_ip_id,
+                                               cap, cap_blocks, d_reply, d_start, d_len, d_src, d_n, d_ws, c->d_echo, hs);
+  if (e != hipSuccess) return hip_fail(e, "echo reply kernels launch");
   return LNX_OK;
 }
 

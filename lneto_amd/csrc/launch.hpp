@@ -56,6 +56,15 @@ hipError_t launch_rst_frames(const lnx_rst_cfg& cfg, const lnx_tcp_rst* entry, u
                              uint8_t* reply, const uint32_t* image, hipStream_t stream);
 }  // namespace lnxr
 
+// echo_kernel.hip: echo replies for ICMPv4 echo requests
+namespace lnxe {
+uint64_t echo_ws_bytes(uint64_t n);
+hipError_t launch_echo_reply(const uint8_t* bytes, const uint64_t* off, uint64_t n, uint32_t trim, const lnx_rx_delivery* rec,
+                             const lnx_rst_cfg& cfg, const uint16_t* ip_id, uint64_t cap, uint64_t cap_blocks, uint8_t* reply,
+                             uint64_t* start, uint32_t* len, uint32_t* src, uint32_t* d_n, void* ws, const uint32_t* image,
+                             hipStream_t stream);
+}  // namespace lnxe
+
 namespace lnx {
 
 // api.cpp: the current device's images and CU count, and the thread's lnx_last_error

@@ -181,6 +181,18 @@ std::vector<uint32_t> build_rst_image() {
   return img;
 }
 
+// The echo reply image (table_layout.hpp kEchoImgZ).
+std::vector<uint32_t> build_echo_image() {
+  std::vector<uint32_t> img(kEchoImageDwords);
+  for (uint32_t t = 1; t <= kEchoZ; ++t) {
+    const Z z(4 * (int64_t)t);
+    for (uint32_t i = 0; i < 8; ++i)
+      for (uint32_t v = 0; v < 16; ++v) img[echo_nib(t, i, v)] = z(v << (4 * i));
+  }
+  fill_byte4(img.data() + kEchoImgB, 4 * (int64_t)kEchoZ);
+  return img;
+}
+
 // The CRC32Search tables (table_layout.hpp k*Off).
 std::vector<uint32_t> build_search_tables() {
   std::vector<uint32_t> img(kSearchTableDwords);

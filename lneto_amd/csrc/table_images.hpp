@@ -12,5 +12,6 @@ std::vector<uint32_t> build_stage_image();              // table_layout.hpp: kSt
 std::vector<uint32_t> build_rx_image();                 // kRxImageDwords
 std::vector<uint32_t> build_search_tables();            // kSearchTableDwords
 std::vector<uint32_t> build_rst_image();                // kRstImageDwords
+std::vector<uint32_t> build_echo_image();               // kEchoImageDwords
 
 }  // namespace lnx

@@ -1,7 +1,7 @@
 // table_layout.hpp — dword layout of the table images that table_images.cpp
 // builds on the host and the kernels read from HBM: the staged lane streams'
-// image, the receive / transmit image, the CRC32Search tables and the RST
-// reply image.  (The CRC
+// image, the receive / transmit image, the CRC32Search tables and the RST and
+// echo reply images.  (The CRC
 // rows' LDS images are in lds_layout.hpp.)  Each region starts where the one
 // before it ends; both sides take every offset from here.
 //
@@ -71,6 +71,15 @@ constexpr uint32_t kRstImageDwords = kRstImgZ + kRstLanes * kNib8Dwords;
 // (an odd p keeps its nibble tables in swapped pairs: the sixteen lanes of a row, one p each, reach all 32 LDS banks)
 constexpr uint32_t rst_nib(uint32_t p, uint32_t i, uint32_t v) { return nib8_at(kRstImgZ + kNib8Dwords * p, i ^ (p & 1u), v); }
 static_assert(kRstImageDwords == 1920, "RST reply image");
+
+// ---- the echo reply image (echo_kernel.hip: echo_plan.hpp echo_fcs_part)
+constexpr uint32_t kEchoZ = 64;                                         // the dwords a wave folds in one step
+constexpr uint32_t kEchoImgZ = 0;                                       // Z_{4t} nibble tables, 1 <= t <= 64: the share of a dword t dwords before the end
+constexpr uint32_t kEchoImgB = kEchoImgZ + kEchoZ * kNib8Dwords;         // Z_256 byte tables: a lane's own register over one more step of the wave
+constexpr uint32_t kEchoImageDwords = kEchoImgB + kByte4Dwords;
+// (an odd t keeps its nibble tables in swapped pairs, as the RST image does)
+constexpr uint32_t echo_nib(uint32_t t, uint32_t i, uint32_t v) { return nib8_at(kEchoImgZ + kNib8Dwords * (t - 1u), i ^ (t & 1u), v); }
+static_assert(kEchoImgB == 8192 && kEchoImageDwords == 9216, "echo reply image");
 
 // the values every reader of these images was written against
 static_assert(kStageZ8Img == 5504 && kStageNibHiImg == 14720 && kStageImageDwords == 15872, "staged image");
