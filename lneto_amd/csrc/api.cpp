@@ -28,6 +28,37 @@ int hip_fail(hipError_t e, const char* what) {
   return LNX_EHIP;
 }
 
+bool misaligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
+
+// The n == 0 path of the entries that report counts: `words` zero words at p, when the caller gave a p.
+int zero_words(uint32_t* p, uint32_t words, hipStream_t hs, const char* what) {
+  if (!p) return LNX_OK;
+  const hipError_t e = hipMemsetAsync(p, 0, words * sizeof(uint32_t), hs);
+  return e == hipSuccess ? LNX_OK : hip_fail(e, what);
+}
+
+// What the two delivery entries refuse alike (`allowed`: the entry's flag bits).
+bool deliver_args_ok(const lnx_rx_filter* filter, RxFilter* filt, uint32_t flags, uint32_t allowed, const lnx_rx_ports* ports,
+                     uint64_t n, const lnx_rx_delivery* d_rec, const uint32_t* d_order, const uint32_t* d_count,
+                     const void* d_ws) {
+  if (!rx_filter_of(filter, filt)) return false;
+  if (flags & ~allowed) return false;
+  if (ports && (ports->n_tcp > 256u || ports->n_udp > 256u)) return false;
+  if ((d_order == nullptr) != (d_count == nullptr)) return false;
+  if (n >> 32) return false;
+  return !(misaligned(d_rec, 16) || misaligned(d_order, 4) || misaligned(d_count, 4) || misaligned(d_ws, 4));
+}
+
+// What the two record-driven reply entries refuse alike (ws_align: of the entry's workspace).
+bool reply_args_ok(uint32_t flags, const lnx_rst_cfg* cfg, uint64_t n, const uint8_t* d_reply, const lnx_rx_delivery* d_rec,
+                   const uint32_t* d_src, const uint32_t* d_n, const void* d_ws, uintptr_t ws_align, const uint16_t* d_ip_id) {
+  if (flags & ~(uint32_t)LNX_RX_NO_FCS) return false;
+  if (cfg && (cfg->flags & ~(uint32_t)LNX_TX_FCS)) return false;
+  if (n >> 32) return false;
+  return !(misaligned(d_reply, 64) || misaligned(d_rec, 16) || misaligned(d_src, 4) || misaligned(d_n, 4) ||
+           misaligned(d_ws, ws_align) || misaligned(d_ip_id, 2));
+}
+
 struct DeviceCtx {
   std::mutex mu;                   // serializes initialization
   std::atomic<bool> ready{false};  // set once every field below is valid
@@ -610,19 +641,9 @@ int lnx_rx_deliver_batch(const uint8_t* d_bytes, const uint64_t* d_off, uint64_t
                          const uint8_t* d_verdict, lnx_rx_delivery* d_rec, uint32_t* d_order, uint32_t* d_count,
                          void* d_ws, void* stream) {
   RxFilter filt;
-  if (!rx_filter_of(filter, &filt)) return LNX_EINVAL;
-  if (flags & ~(uint32_t)LNX_RX_NO_FCS) return LNX_EINVAL;
-  if (ports && (ports->n_tcp > 256u || ports->n_udp > 256u)) return LNX_EINVAL;
-  if ((d_order == nullptr) != (d_count == nullptr)) return LNX_EINVAL;
-  if (n >> 32) return LNX_EINVAL;
-  auto misaligned = [](const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; };
-  if (misaligned(d_rec, 16) || misaligned(d_order, 4) || misaligned(d_count, 4) || misaligned(d_ws, 4)) return LNX_EINVAL;
+  if (!deliver_args_ok(filter, &filt, flags, LNX_RX_NO_FCS, ports, n, d_rec, d_order, d_count, d_ws)) return LNX_EINVAL;
   const hipStream_t hs = static_cast<hipStream_t>(stream);
-  if (n == 0) {
-    if (!d_count) return LNX_OK;
-    const hipError_t e = hipMemsetAsync(d_count, 0, (LNX_H_COUNT + 1u) * sizeof(uint32_t), hs);
-    return e == hipSuccess ? LNX_OK : hip_fail(e, "hipMemsetAsync(d_count)");
-  }
+  if (n == 0) return zero_words(d_count, LNX_H_COUNT + 1u, hs, "hipMemsetAsync(d_count)");
   if (!d_bytes || !d_off || !d_verdict || !d_rec || (d_order && !d_ws)) return LNX_EINVAL;
   const hipError_t e = lnxd::launch_deliver(d_bytes, d_off, n, (flags & LNX_RX_NO_FCS) ? 0u : 4u, filt, ports, d_fcs_ok,
                                             d_verdict, d_rec, d_order, d_count, d_ws, hs);
@@ -639,19 +660,11 @@ int lnx_rx_verify_deliver_batch(const uint8_t* d_bytes, const uint64_t* d_off, u
                                 uint8_t* d_verdict, lnx_rx_delivery* d_rec, uint32_t* d_order, uint32_t* d_count,
                                 void* d_ws, void* stream) {
   RxFilter filt;
-  if (!rx_filter_of(filter, &filt)) return LNX_EINVAL;
-  if (flags & ~(uint32_t)(LNX_VERIFY_EVIL_BIT | LNX_VERIFY_ICMP | LNX_RX_NO_FCS)) return LNX_EINVAL;
-  if (ports && (ports->n_tcp > 256u || ports->n_udp > 256u)) return LNX_EINVAL;
-  if ((d_order == nullptr) != (d_count == nullptr)) return LNX_EINVAL;
-  if (n >> 32) return LNX_EINVAL;
-  auto misaligned = [](const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; };
-  if (misaligned(d_rec, 16) || misaligned(d_order, 4) || misaligned(d_count, 4) || misaligned(d_ws, 4)) return LNX_EINVAL;
+  if (!deliver_args_ok(filter, &filt, flags, LNX_VERIFY_EVIL_BIT | LNX_VERIFY_ICMP | LNX_RX_NO_FCS, ports, n, d_rec, d_order,
+                       d_count, d_ws))
+    return LNX_EINVAL;
   const hipStream_t hs = static_cast<hipStream_t>(stream);
-  if (n == 0) {
-    if (!d_count) return LNX_OK;
-    const hipError_t e = hipMemsetAsync(d_count, 0, (LNX_H_COUNT + 1u) * sizeof(uint32_t), hs);
-    return e == hipSuccess ? LNX_OK : hip_fail(e, "hipMemsetAsync(d_count)");
-  }
+  if (n == 0) return zero_words(d_count, LNX_H_COUNT + 1u, hs, "hipMemsetAsync(d_count)");
   if (!d_bytes || !d_off || !d_fcs_ok || !d_verdict || !d_rec || (d_order && !d_ws)) return LNX_EINVAL;
   DeviceCtx* c = nullptr;
   int st = get_ctx(&c);
@@ -674,19 +687,9 @@ uint64_t lnx_rx_rst_ws_bytes(uint64_t n) { return lnxr::rst_ws_bytes(n); }
 int lnx_rx_rst_reply_batch(const uint8_t* d_bytes, const uint64_t* d_off, uint64_t n, uint32_t flags,
                            const lnx_rx_delivery* d_rec, const lnx_rst_cfg* cfg, const uint16_t* d_ip_id, uint64_t cap,
                            uint8_t* d_reply, uint32_t* d_src, uint32_t* d_n, void* d_ws, void* stream) {
-  if (flags & ~(uint32_t)LNX_RX_NO_FCS) return LNX_EINVAL;
-  if (cfg && (cfg->flags & ~(uint32_t)LNX_TX_FCS)) return LNX_EINVAL;
-  if (n >> 32) return LNX_EINVAL;
-  auto misaligned = [](const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; };
-  if (misaligned(d_reply, 64) || misaligned(d_rec, 16) || misaligned(d_src, 4) || misaligned(d_n, 4) ||
-      misaligned(d_ws, 4) || misaligned(d_ip_id, 2))
-    return LNX_EINVAL;
+  if (!reply_args_ok(flags, cfg, n, d_reply, d_rec, d_src, d_n, d_ws, 4, d_ip_id)) return LNX_EINVAL;
   const hipStream_t hs = static_cast<hipStream_t>(stream);
-  if (n == 0) {
-    if (!d_n) return LNX_OK;
-    const hipError_t e = hipMemsetAsync(d_n, 0, 2 * sizeof(uint32_t), hs);
-    return e == hipSuccess ? LNX_OK : hip_fail(e, "hipMemsetAsync(d_n)");
-  }
+  if (n == 0) return zero_words(d_n, 2, hs, "hipMemsetAsync(d_n)");
   if (!d_bytes || !d_off || !d_rec || !cfg || !d_n || !d_ws) return LNX_EINVAL;
   if (cap > 0 && (!d_ip_id || !d_reply || !d_src)) return LNX_EINVAL;
   DeviceCtx* c = nullptr;
@@ -701,7 +704,6 @@ int lnx_rx_rst_reply_batch(const uint8_t* d_bytes, const uint64_t* d_off, uint64
 int lnx_tcp_rst_frames_batch(const lnx_rst_cfg* cfg, const lnx_tcp_rst* d_entry, uint64_t n, const uint16_t* d_ip_id,
                              uint8_t* d_reply, void* stream) {
   if (cfg && (cfg->flags & ~(uint32_t)LNX_TX_FCS)) return LNX_EINVAL;
-  auto misaligned = [](const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; };
   if (misaligned(d_reply, 64) || misaligned(d_entry, 4) || misaligned(d_ip_id, 2)) return LNX_EINVAL;
   if (n == 0) return LNX_OK;
   if (!cfg || !d_entry || !d_ip_id || !d_reply) return LNX_EINVAL;
@@ -722,19 +724,10 @@ int lnx_rx_echo_reply_batch(const uint8_t* d_bytes, const uint64_t* d_off, uint6
                             const lnx_rx_delivery* d_rec, const lnx_rst_cfg* cfg, const uint16_t* d_ip_id,
                             uint64_t cap, uint64_t cap_blocks, uint8_t* d_reply, uint64_t* d_start,
                             uint32_t* d_len, uint32_t* d_src, uint32_t* d_n, void* d_ws, void* stream) {
-  if (flags & ~(uint32_t)LNX_RX_NO_FCS) return LNX_EINVAL;
-  if (cfg && (cfg->flags & ~(uint32_t)LNX_TX_FCS)) return LNX_EINVAL;
-  if (n >> 32) return LNX_EINVAL;
-  auto misaligned = [](const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; };
-  if (misaligned(d_reply, 64) || misaligned(d_rec, 16) || misaligned(d_start, 8) || misaligned(d_len, 4) ||
-      misaligned(d_src, 4) || misaligned(d_n, 4) || misaligned(d_ws, 8) || misaligned(d_ip_id, 2))
-    return LNX_EINVAL;
+  if (!reply_args_ok(flags, cfg, n, d_reply, d_rec, d_src, d_n, d_ws, 8, d_ip_id)) return LNX_EINVAL;
+  if (misaligned(d_start, 8) || misaligned(d_len, 4)) return LNX_EINVAL;
   const hipStream_t hs = static_cast<hipStream_t>(stream);
-  if (n == 0) {
-    if (!d_n) return LNX_OK;
-    const hipError_t e = hipMemsetAsync(d_n, 0, 4 * sizeof(uint32_t), hs);
-    return e == hipSuccess ? LNX_OK : hip_fail(e, "hipMemsetAsync(d_n)");
-  }
+  if (n == 0) return zero_words(d_n, 4, hs, "hipMemsetAsync(d_n)");
   if (!d_bytes || !d_off || !d_rec || !cfg || !d_n || !d_ws) return LNX_EINVAL;
   if (cap > 0 && cap_blocks > 0 && (!d_ip_id || !d_reply || !d_start || !d_len || !d_src)) return LNX_EINVAL;
   DeviceCtx* c = nullptr;

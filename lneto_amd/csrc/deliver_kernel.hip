@@ -8,6 +8,7 @@
 // workgroup (no look-back, no grid barrier, no spin; the launches' order on the
 // stream is the only dependency):
 //   records   one 16-lane row per frame, header bytes only;
+// then the slice walk of slice_walk.hpp, a count per bucket:
 //   histogram each workgroup counts the buckets of ONE contiguous index slice;
 //   scan      per bucket, over the workgroups in index order;
 //   scatter   each workgroup walks its slice again in index order.
@@ -18,7 +19,7 @@
 #include "deliver_plan.hpp"
 #include "launch.hpp"
 #include "rx_filter.hpp"
-#include "wave_util.hpp"
+#include "slice_walk.hpp"
 
 namespace lnxd {
 
@@ -64,9 +65,7 @@ deliver_records_kernel(const uint8_t* __restrict__ bytes, const uint64_t* __rest
     const uint64_t f = g + row;
     const bool valid = f < n;
     const uint64_t s = valid ? off[f] : 0, e = valid ? off[f + 1] : 0;
-    const uint64_t lt = e > s ? e - s : 0;  // an end below its start: an empty frame
-    const uint32_t Lt = lt < 0x7FFFFFFFull ? (uint32_t)lt : 0x7FFFFFFFu;
-    const uint32_t L = Lt > trim ? Lt - trim : 0u;
+    const uint32_t L = lnx::frame_len(s, e, trim);
     const uint8_t* p = bytes + s;
     const uint32_t q = (uint32_t)(reinterpret_cast<uintptr_t>(p) & 3u);
     const uint32_t ndw = L == 0 ? 0u : (q + (L < kWinFrame ? L : kWinFrame) + 3u) >> 2;  // <= kWinDwords
@@ -108,17 +107,7 @@ deliver_records_kernel(const uint8_t* __restrict__ bytes, const uint64_t* __rest
 }
 
 // ------------------------------------------------------------------ grouping
-// Workgroup g of G owns the index slice [lo, hi): `per` consecutive chunks of
-// kGrpBlock frames, per = ceil(chunks / G); the last workgroups' slices may be
-// short or empty.  The histogram and the scatter launch use the same G.
-__device__ __forceinline__ void grp_slice(uint64_t n, uint64_t& lo, uint64_t& hi) {
-  const uint64_t chunks = (n + kGrpBlock - 1) / kGrpBlock;
-  const uint64_t per = (chunks + gridDim.x - 1) / gridDim.x;
-  lo = (uint64_t)blockIdx.x * per * kGrpBlock;
-  lo = lo < n ? lo : n;
-  hi = lo + per * kGrpBlock;
-  hi = hi < n ? hi : n;
-}
+// The histogram and the scatter launch walk the same slices (slice_walk.hpp slice_bounds).
 __device__ __forceinline__ uint32_t grp_key(const uint16_t* keys, uint64_t i) {
   const uint32_t k = keys[i];
   return k < kBuckets ? k : kBuckets - 1u;  // (the records launch writes nothing larger)
@@ -131,7 +120,7 @@ deliver_hist_kernel(const uint16_t* __restrict__ keys, uint64_t n, uint32_t* __r
   for (uint32_t b = threadIdx.x; b < kBuckets; b += kGrpBlock) h[b] = 0;
   __syncthreads();
   uint64_t lo, hi;
-  grp_slice(n, lo, hi);
+  lnx::slice_bounds(n, kGrpBlock, lo, hi);
   for (uint64_t i = lo + threadIdx.x; i < hi; i += kGrpBlock) atomicAdd(&h[grp_key(keys, i)], 1u);
   __syncthreads();
   for (uint32_t b = threadIdx.x; b < kBuckets; b += kGrpBlock) hist[(uint64_t)blockIdx.x * kBuckets + b] = h[b];
@@ -190,15 +179,7 @@ deliver_scatter_kernel(const uint16_t* __restrict__ keys, uint64_t n, const uint
       c[j] = b < kBuckets ? count[b] : 0u;
       sum += c[j];
     }
-    part[t] = sum;
-    __syncthreads();
-    for (uint32_t d = 1; d < (uint32_t)kGrpBlock; d <<= 1) {
-      const uint32_t v = t >= d ? part[t - d] : 0u;
-      __syncthreads();
-      part[t] += v;
-      __syncthreads();
-    }
-    uint32_t base = part[t] - sum;
+    uint32_t base = lnx::block_scan_inclusive<kGrpBlock>(part, sum) - sum;
 #pragma unroll
     for (uint32_t j = 0; j < 5; ++j) {
       const uint32_t b = 5u * t + j;
@@ -208,7 +189,7 @@ deliver_scatter_kernel(const uint16_t* __restrict__ keys, uint64_t n, const uint
     __syncthreads();
   }
   uint64_t lo, hi;
-  grp_slice(n, lo, hi);
+  lnx::slice_bounds(n, kGrpBlock, lo, hi);
   for (uint64_t c0 = lo; c0 < hi; c0 += kGrpBlock) {  // (uniform: every wave keeps all its lanes)
     const uint64_t i = c0 + t;
     const bool live = i < hi;
@@ -239,15 +220,12 @@ deliver_scatter_kernel(const uint16_t* __restrict__ keys, uint64_t n, const uint
 }
 
 // ws: the workgroups' histograms (G x kBuckets words), then the frames' keys
-static uint32_t grp_grid(uint64_t n) {
-  const uint64_t chunks = (n + kGrpBlock - 1) / kGrpBlock;
-  return (uint32_t)(chunks < kGrpGridCap ? (chunks ? chunks : 1) : kGrpGridCap);
-}
-uint64_t deliver_ws_bytes(uint64_t n) { return (uint64_t)grp_grid(n) * kBuckets * 4u + 2u * n; }
+static uint32_t grp_workgroups(uint64_t n) { return lnx::slice_grid(n, kGrpBlock, kGrpGridCap); }
+uint64_t deliver_ws_bytes(uint64_t n) { return (uint64_t)grp_workgroups(n) * kBuckets * 4u + 2u * n; }
 
 // the keys' place in ws (n: the frames the grouping launches will take)
 uint16_t* deliver_keys(void* ws, uint64_t n) {
-  return reinterpret_cast<uint16_t*>(static_cast<uint32_t*>(ws) + (uint64_t)grp_grid(n) * kBuckets);
+  return reinterpret_cast<uint16_t*>(static_cast<uint32_t*>(ws) + (uint64_t)grp_workgroups(n) * kBuckets);
 }
 
 // The three grouping launches over keys that launches before them on `stream`
@@ -255,7 +233,7 @@ uint16_t* deliver_keys(void* ws, uint64_t n) {
 // that writes records and keys itself (rx_verify_kernel.hip).
 hipError_t launch_deliver_group(uint64_t n, uint32_t* order, uint32_t* count, void* ws, hipStream_t stream) {
   if (n == 0) return hipSuccess;
-  const uint32_t G = grp_grid(n);
+  const uint32_t G = grp_workgroups(n);
   uint32_t* hist = static_cast<uint32_t*>(ws);
   const uint16_t* keys = deliver_keys(ws, n);
   hipError_t e;

@@ -2,9 +2,9 @@
 // §3.20): the frame of every delivery record that queues an echo entry
 // (echo_plan.hpp), in arrival order, each in whole 64-byte blocks of d_reply.
 //
-// Three launches on the caller's stream in the shape of reply_kernel.hip, none of
-// which waits for another workgroup (no look-back, no grid barrier, no spin, no
-// global atomics; the launches' order on the stream is the only dependency):
+// Three launches on the caller's stream, the slice walk of slice_walk.hpp, none
+// of which waits for another workgroup (no look-back, no grid barrier, no spin,
+// no global atomics; the launches' order on the stream is the only dependency):
 //   count  each workgroup counts the queueing frames of ONE contiguous index
 //          slice and the blocks their replies take (from the records and the
 //          few header bytes of rules 3-4; the data is never read);
@@ -29,8 +29,8 @@
 #include <cstdint>
 #include "echo_plan.hpp"
 #include "launch.hpp"
+#include "slice_walk.hpp"
 #include "table_layout.hpp"
-#include "wave_util.hpp"
 
 namespace lnxe {
 
@@ -44,26 +44,6 @@ constexpr uint32_t kEpRowSteps = kEpRowBlocks; // 16 dwords a step
 // flight together; a longer one is read twice (tests: WAVE_BLOCKS)
 constexpr uint32_t kEpWaveSteps = 8, kEpWaveBlocks = 4 * kEpWaveSteps;
 
-// Workgroup g of G owns the index slice [lo, hi): `per` consecutive chunks of
-// kEpBlock frames, per = ceil(chunks / G).  The count and the build launch use the same G.
-__device__ __forceinline__ void ep_slice(uint64_t n, uint64_t& lo, uint64_t& hi) {
-  const uint64_t chunks = (n + kEpBlock - 1) / kEpBlock;
-  const uint64_t per = (chunks + gridDim.x - 1) / gridDim.x;
-  lo = (uint64_t)blockIdx.x * per * kEpBlock;
-  lo = lo < n ? lo : n;
-  hi = lo + per * kEpBlock;
-  hi = hi < n ? hi : n;
-}
-
-// The frame's fields from its own aligned dwords only: a dword that holds a
-// byte below L lies in that byte's page, so nothing else is loaded.
-__device__ __forceinline__ uint32_t ep_dword(const uint8_t* a) {
-  return *reinterpret_cast<const uint32_t*>(reinterpret_cast<uintptr_t>(a) & ~(uintptr_t)3);
-}
-__device__ __forceinline__ uint32_t ep_byte(const uint8_t* a) {
-  return (ep_dword(a) >> (8u * (uint32_t)(reinterpret_cast<uintptr_t>(a) & 3u))) & 0xFFu;
-}
-
 // Frame i under record i: does it queue an entry (rules 1-4)?  A frame whose
 // record has another handler or verdict costs its record and nothing else; a
 // candidate its two offsets and bytes l4 and 14.  p, l4, end: the frame's start
@@ -73,15 +53,13 @@ __device__ __forceinline__ bool ep_queues(const uint8_t* __restrict__ bytes, con
                                           uint32_t& l4, uint32_t& end) {
   const uint4 r = rec[i];  // lnx_rx_delivery: ip_end; handler | l4_off << 16; the ports; verdict | flags << 8
   if ((r.w & 0xFFu) != 0 || (r.y & 0xFFFFu) != kHandlerIcmp4) return false;
-  const uint64_t s = off[i], e = off[i + 1];
-  const uint64_t lt = e > s ? e - s : 0;  // an end below its start: an empty frame
-  const uint32_t Lt = lt < 0x7FFFFFFFull ? (uint32_t)lt : 0x7FFFFFFFu;
-  const uint32_t L = Lt > trim ? Lt - trim : 0u;
+  const uint64_t s = off[i];
+  const uint32_t L = lnx::frame_len(s, off[i + 1], trim);
   p = bytes + s;
   l4 = r.y >> 16;
   end = r.x;
   const uint8_t* pp = p;
-  return echo_queues(L, 0u, kHandlerIcmp4, l4, end, [pp](uint32_t o) -> uint32_t { return ep_byte(pp + o); });
+  return echo_queues(L, 0u, kHandlerIcmp4, l4, end, [pp](uint32_t o) -> uint32_t { return lnx::own_byte(pp + o); });
 }
 
 // ------------------------------------------------------------------ count, scan
@@ -98,7 +76,7 @@ echo_count_kernel(const uint8_t* __restrict__ bytes, const uint64_t* __restrict_
   __shared__ uint32_t wcnt[kEpWaves];
   __shared__ uint64_t wblk[kEpWaves];
   uint64_t lo, hi;
-  ep_slice(n, lo, hi);
+  lnx::slice_bounds(n, kEpBlock, lo, hi);
   uint32_t c = 0;
   uint64_t b = 0;
   for (uint64_t c0 = lo; c0 < hi; c0 += kEpBlock) {  // (uniform)
@@ -132,21 +110,13 @@ echo_scan_kernel(void* __restrict__ ws, uint32_t G, uint64_t cap, uint64_t cap_b
   const uint32_t t = threadIdx.x;
   const uint32_t c = t < G ? cnt[t] : 0u;
   const uint64_t b = t < G ? blk[t] : 0u;
-  part[t] = c;
-  partb[t] = b;
-  __syncthreads();
-  for (uint32_t d = 1; d < kEpGridCap; d <<= 1) {
-    const uint32_t v = t >= d ? part[t - d] : 0u;
-    const uint64_t vb = t >= d ? partb[t - d] : 0u;
-    __syncthreads();
-    part[t] += v;
-    partb[t] += vb;
-    __syncthreads();
-  }
-  if (t < G) cnt[t] = part[t] - c, blk[t] = partb[t] - b;
-  if (t == G - 1u) {
-    const uint32_t total = part[t];  // (n < 2^32)
-    const uint64_t totalb = partb[t];
+  lnx::ScanSlot<uint32_t> sc{part, c, 0u};
+  lnx::ScanSlot<uint64_t> sb{partb, b, 0u};
+  lnx::block_scan_inclusive<kEpGridCap>(sc, sb);  // the two sums in the same rounds
+  if (t < G) cnt[t] = sc.v - c, blk[t] = sb.v - b;
+  if (t == G - 1u) {  // the last workgroup's inclusive sums: the totals
+    const uint32_t total = sc.v;  // (n < 2^32)
+    const uint64_t totalb = sb.v;
     cnt[G] = total, blk[G] = totalb;
     const bool fits = total <= cap && totalb <= cap_blocks;
     d_n[0] = fits ? total : 0u;
@@ -294,17 +264,6 @@ __device__ __forceinline__ void ep_tables(uint32_t* tab, const uint32_t* __restr
   for (uint32_t i = threadIdx.x; i < lnx::kEchoImageDwords; i += kEpBlock) tab[i] = image[lnx::kEchoImgZ + i];
 }
 
-// An inclusive prefix sum over the wave's lanes.
-__device__ __forceinline__ uint32_t ep_wave_scan(uint32_t v) {
-  const uint32_t lane = threadIdx.x & 63u;
-#pragma unroll
-  for (uint32_t d = 1; d < 64; d <<= 1) {
-    const uint32_t o = (uint32_t)__shfl_up((int)v, d, 64);
-    v += lane >= d ? o : 0u;
-  }
-  return v;
-}
-
 // ------------------------------------------------------------------ build
 // run, brun: the queueing frames and their blocks before the chunk (the scan's
 // bases of this workgroup, then the chunks walked).  Reply k with first block b
@@ -337,7 +296,7 @@ echo_reply_kernel(const uint8_t* __restrict__ bytes, const uint64_t* __restrict_
   const uint32_t fixed16 = echo_fixed_word((t & 15u) < kEchoHdrWords ? (t & 15u) : kEchoHdrWords - 1u, cfg);
   const uint32_t fixed64 = echo_fixed_word((t & 63u) < kEchoHdrWords ? (t & 63u) : kEchoHdrWords - 1u, cfg);
   uint64_t lo, hi;
-  ep_slice(n, lo, hi);
+  lnx::slice_bounds(n, kEpBlock, lo, hi);
   for (uint64_t c0 = lo; c0 < hi && run < cap && brun < cap_blocks; c0 += kEpBlock) {  // (uniform: every wave keeps all its lanes)
     const uint64_t i = c0 + t;
     const uint8_t* p = bytes;
@@ -345,22 +304,16 @@ echo_reply_kernel(const uint8_t* __restrict__ bytes, const uint64_t* __restrict_
     const bool q = i < hi && ep_queues(bytes, off, trim, rec, i, p, l4, end);
     const uint32_t d = q ? end - l4 - 8u : 0u;
     const uint32_t nb = q ? echo_blocks(d, FCS) : 0u;
-    const uint64_t m64 = __builtin_amdgcn_ballot_w64(q);
-    const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(m64 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m64, 0u));
-    const uint32_t binc = ep_wave_scan(nb);
+    uint32_t below, wq;
+    lnx::wave_rank(q, below, wq);
+    const uint32_t binc = lnx::wave_scan_add(nb);
     __syncthreads();  // the last chunk's rows and waves are done with st and the counts (and, first, the tables' stores)
-    if ((t & 63u) == 0) wcnt[wave] = (uint32_t)__builtin_popcountll(m64);
+    if ((t & 63u) == 0) wcnt[wave] = wq;
     if ((t & 63u) == 63u) wblk[wave] = binc;
     __syncthreads();
-    uint32_t before = 0, total = 0, bbefore = 0, btotal = 0;
-#pragma unroll
-    for (uint32_t w = 0; w < kEpWaves; ++w) {
-      const uint32_t v = wcnt[w], vb = wblk[w];
-      before += w < wave ? v : 0u;
-      total += v;
-      bbefore += w < wave ? vb : 0u;
-      btotal += vb;
-    }
+    uint32_t before, total, bbefore, btotal;
+    lnx::waves_before<kEpWaves>(wcnt, wave, before, total);
+    lnx::waves_before<kEpWaves>(wblk, wave, bbefore, btotal);
     const uint32_t r = before + below;           // < kEpBlock
     const uint32_t b = bbefore + binc - nb;      // the reply's first block, from the chunk's
     const bool wr = q && run + r < cap && brun + b + nb <= cap_blocks;
@@ -369,9 +322,9 @@ echo_reply_kernel(const uint8_t* __restrict__ bytes, const uint64_t* __restrict_
     if ((t & 63u) == 0) wwr[wave] = (uint32_t)__builtin_popcountll(w64), wshort[wave] = (uint32_t)__builtin_popcountll(s64);
     if (wr) {
       const uint8_t* pp = p;
-      const uint32_t id = (ep_byte(pp + l4 + 4u) << 8) | ep_byte(pp + l4 + 5u);
+      const uint32_t id = (lnx::own_byte(pp + l4 + 4u) << 8) | lnx::own_byte(pp + l4 + 5u);
       uint32_t addr = 0;
-      for (uint32_t k = 0; k < 4; ++k) addr = (addr << 8) | ep_byte(pp + 26u + k);
+      for (uint32_t k = 0; k < 4; ++k) addr = (addr << 8) | lnx::own_byte(pp + 26u + k);
       st.plo[r] = (uint32_t)reinterpret_cast<uintptr_t>(p);
       st.phi[r] = (uint32_t)(reinterpret_cast<uintptr_t>(p) >> 32);
       st.l4[r] = l4;
@@ -422,19 +375,15 @@ echo_reply_kernel(const uint8_t* __restrict__ bytes, const uint64_t* __restrict_
 }
 
 // ------------------------------------------------------------------ launchers
-static uint32_t ep_grid(uint64_t n) {
-  const uint64_t chunks = (n + kEpBlock - 1) / kEpBlock;
-  return (uint32_t)(chunks < kEpGridCap ? (chunks ? chunks : 1) : kEpGridCap);
-}
 // ws: the workgroups' block sums (G + 1 qwords), then their reply counts (G + 1 words)
-uint64_t echo_ws_bytes(uint64_t n) { return (uint64_t)(ep_grid(n) + 1u) * 12u; }
+uint64_t echo_ws_bytes(uint64_t n) { return (uint64_t)(lnx::slice_grid(n, kEpBlock, kEpGridCap) + 1u) * 12u; }
 
 // n > 0.  cap == 0 or cap_blocks == 0: d_n alone is written (count and scan).
 hipError_t launch_echo_reply(const uint8_t* bytes, const uint64_t* off, uint64_t n, uint32_t trim, const lnx_rx_delivery* rec,
                              const lnx_rst_cfg& cfg, const uint16_t* ip_id, uint64_t cap, uint64_t cap_blocks, uint8_t* reply,
                              uint64_t* start, uint32_t* len, uint32_t* src, uint32_t* d_n, void* ws, const uint32_t* image,
                              hipStream_t stream) {
-  const uint32_t G = ep_grid(n);
+  const uint32_t G = lnx::slice_grid(n, kEpBlock, kEpGridCap);
   const RstCfg c = lnxr::rst_cfg_of(cfg);
   const uint4* rb = reinterpret_cast<const uint4*>(rec);
   hipError_t e;

@@ -4,8 +4,8 @@
 //
 // Three launches on the caller's stream, none of which waits for another
 // workgroup (no look-back, no grid barrier, no spin, no global atomics; the
-// launches' order on the stream is the only dependency), in the shape of
-// §3.17's grouping:
+// launches' order on the stream is the only dependency), the slice walk of
+// slice_walk.hpp:
 //   count  each workgroup counts the queueing frames of ONE contiguous index slice;
 //   scan   over the workgroups in index order (one workgroup), and d_n;
 //   build  each workgroup walks its slice again in index order, a chunk of
@@ -19,8 +19,8 @@
 #include <cstdint>
 #include "launch.hpp"
 #include "reply_plan.hpp"
+#include "slice_walk.hpp"
 #include "table_layout.hpp"
-#include "wave_util.hpp"
 
 namespace lnxr {
 
@@ -31,28 +31,9 @@ constexpr uint32_t kRpGridCap = 512;           // workgroups of the count / buil
 // ... of the explicit-entries launch, grid-strided past it (FRAMES_GRID_CAP in tests/test_rst_reply_grid_mid.py)
 constexpr uint32_t kRpFramesGridCap = 2048;
 
-// Workgroup g of G owns the index slice [lo, hi): `per` consecutive chunks of
-// kRpBlock frames, per = ceil(chunks / G).  The count and the build launch use the same G.
-__device__ __forceinline__ void rp_slice(uint64_t n, uint64_t& lo, uint64_t& hi) {
-  const uint64_t chunks = (n + kRpBlock - 1) / kRpBlock;
-  const uint64_t per = (chunks + gridDim.x - 1) / gridDim.x;
-  lo = (uint64_t)blockIdx.x * per * kRpBlock;
-  lo = lo < n ? lo : n;
-  hi = lo + per * kRpBlock;
-  hi = hi < n ? hi : n;
-}
-
 // ------------------------------------------------------------------ front end: records
-// The frame's fields from its own aligned dwords only: a dword that holds a
-// byte below L lies in that byte's page, so nothing else is loaded.
-__device__ __forceinline__ uint32_t rp_dword(const uint8_t* a) {
-  return *reinterpret_cast<const uint32_t*>(reinterpret_cast<uintptr_t>(a) & ~(uintptr_t)3);
-}
-__device__ __forceinline__ uint32_t rp_byte(const uint8_t* a) {
-  return (rp_dword(a) >> (8u * (uint32_t)(reinterpret_cast<uintptr_t>(a) & 3u))) & 0xFFu;
-}
 __device__ __forceinline__ uint32_t rp_be32(const uint8_t* a) {  // a[0..3] are all the frame's
-  const uint64_t two = ((uint64_t)rp_dword(a + 3) << 32) | rp_dword(a);
+  const uint64_t two = ((uint64_t)lnx::own_dword(a + 3) << 32) | lnx::own_dword(a);
   return __builtin_bswap32((uint32_t)(two >> (8u * (uint32_t)(reinterpret_cast<uintptr_t>(a) & 3u))));
 }
 
@@ -66,14 +47,12 @@ __device__ __forceinline__ bool rp_queues(const uint8_t* __restrict__ bytes, con
   const uint8_t* r = rec + 16u * i;  // lnx_rx_delivery: l4_off at 6, the ports at 8 and 10, flags at 13
   const uint32_t fl = r[13];
   if ((fl & kDlvRst) == 0) return false;
-  const uint64_t s = off[i], e = off[i + 1];
-  const uint64_t lt = e > s ? e - s : 0;  // an end below its start: an empty frame
-  const uint32_t Lt = lt < 0x7FFFFFFFull ? (uint32_t)lt : 0x7FFFFFFFu;
-  const uint32_t L = Lt > trim ? Lt - trim : 0u;
+  const uint64_t s = off[i];
+  const uint32_t L = lnx::frame_len(s, off[i + 1], trim);
   p = bytes + s;
   l4 = *reinterpret_cast<const uint16_t*>(r + 6);
   const uint8_t* pp = p;
-  return rst_queues(L, fl, l4, [pp](uint32_t o) -> uint32_t { return rp_byte(pp + o); });
+  return rst_queues(L, fl, l4, [pp](uint32_t o) -> uint32_t { return lnx::own_byte(pp + o); });
 }
 
 // ------------------------------------------------------------------ count, scan
@@ -82,7 +61,7 @@ rst_count_kernel(const uint8_t* __restrict__ bytes, const uint64_t* __restrict__
                  const uint8_t* __restrict__ rec, uint32_t* __restrict__ counts) {
   __shared__ uint32_t wsum[kRpWaves];
   uint64_t lo, hi;
-  rp_slice(n, lo, hi);
+  lnx::slice_bounds(n, kRpBlock, lo, hi);
   uint32_t c = 0;
   for (uint64_t c0 = lo; c0 < hi; c0 += kRpBlock) {  // (uniform)
     const uint64_t i = c0 + threadIdx.x;
@@ -106,17 +85,10 @@ rst_scan_kernel(uint32_t* __restrict__ counts, uint32_t G, uint64_t cap, uint32_
   __shared__ uint32_t part[kRpGridCap];
   const uint32_t t = threadIdx.x;
   const uint32_t c = t < G ? counts[t] : 0u;
-  part[t] = c;
-  __syncthreads();
-  for (uint32_t d = 1; d < kRpGridCap; d <<= 1) {
-    const uint32_t v = t >= d ? part[t - d] : 0u;
-    __syncthreads();
-    part[t] += v;
-    __syncthreads();
-  }
-  if (t < G) counts[t] = part[t] - c;
-  if (t == kRpGridCap - 1u) {
-    const uint32_t total = part[t];  // (n < 2^32)
+  const uint32_t inc = lnx::block_scan_inclusive<kRpGridCap>(part, c);
+  if (t < G) counts[t] = inc - c;
+  if (t == G - 1u) {  // the last workgroup's inclusive sum: the total
+    const uint32_t total = inc;  // (n < 2^32)
     d_n[0] = total < cap ? total : (uint32_t)cap;
     d_n[1] = total;
   }
@@ -181,25 +153,20 @@ rst_reply_kernel(const uint8_t* __restrict__ bytes, const uint64_t* __restrict__
   const uint32_t t = threadIdx.x, wave = t >> 6;
   rp_tables(tab, image);
   uint64_t lo, hi;
-  rp_slice(n, lo, hi);
+  lnx::slice_bounds(n, kRpBlock, lo, hi);
   uint64_t run = base[blockIdx.x];
   for (uint64_t c0 = lo; c0 < hi && run < cap; c0 += kRpBlock) {  // (uniform: every wave keeps all its lanes)
     const uint64_t i = c0 + t;
     const uint8_t* p = bytes;
     uint32_t l4 = 0;
     const bool q = i < hi && rp_queues(bytes, off, trim, rec, i, p, l4);
-    const uint64_t m64 = __builtin_amdgcn_ballot_w64(q);
-    const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(m64 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m64, 0u));
+    uint32_t below, wq;
+    lnx::wave_rank(q, below, wq);
     __syncthreads();  // the last chunk's rows are done with st and wcnt (and, first, the tables' stores)
-    if ((t & 63u) == 0) wcnt[wave] = (uint32_t)__builtin_popcountll(m64);
+    if ((t & 63u) == 0) wcnt[wave] = wq;
     __syncthreads();
-    uint32_t before = 0, total = 0;
-#pragma unroll
-    for (uint32_t w = 0; w < kRpWaves; ++w) {
-      const uint32_t v = wcnt[w];
-      before += w < wave ? v : 0u;
-      total += v;
-    }
+    uint32_t before, total;
+    lnx::waves_before<kRpWaves>(wcnt, wave, before, total);
     const uint32_t r = before + below;  // < kRpBlock
     if (q && run + r < cap) {
       const uint8_t* pp = p;
@@ -248,18 +215,14 @@ rst_frames_kernel(const uint32_t* __restrict__ entry, uint64_t n, RstCfg cfg, co
 }
 
 // ------------------------------------------------------------------ launchers
-static uint32_t rp_grid(uint64_t n) {
-  const uint64_t chunks = (n + kRpBlock - 1) / kRpBlock;
-  return (uint32_t)(chunks < kRpGridCap ? (chunks ? chunks : 1) : kRpGridCap);
-}
 // ws: the workgroups' counts, then bases (G words)
-uint64_t rst_ws_bytes(uint64_t n) { return (uint64_t)rp_grid(n) * 4u; }
+uint64_t rst_ws_bytes(uint64_t n) { return (uint64_t)lnx::slice_grid(n, kRpBlock, kRpGridCap) * 4u; }
 
 // n > 0.  cap == 0: d_n alone is written (count and scan).
 hipError_t launch_rst_reply(const uint8_t* bytes, const uint64_t* off, uint64_t n, uint32_t trim, const lnx_rx_delivery* rec,
                             const lnx_rst_cfg& cfg, const uint16_t* ip_id, uint64_t cap, uint8_t* reply, uint32_t* src,
                             uint32_t* d_n, void* ws, const uint32_t* image, hipStream_t stream) {
-  const uint32_t G = rp_grid(n);
+  const uint32_t G = lnx::slice_grid(n, kRpBlock, kRpGridCap);
   const RstCfg c = rst_cfg_of(cfg);
   const uint8_t* rb = reinterpret_cast<const uint8_t*>(rec);
   uint32_t* counts = static_cast<uint32_t*>(ws);

@@ -1,7 +1,8 @@
 // wave_util.hpp — the small helpers every kernel file shares: byte masks of a
-// loaded word, the RFC 1071 fold, and (device only) the DPP row reductions and
-// the half-word dot product.  The first part is plain C++ that a host compiler
-// also accepts (frame_plan.hpp and its host test use it).
+// loaded word, the RFC 1071 fold, and (device only) the DPP row reductions,
+// the half-word dot product, a lane's rank and the wave prefix sum.  The first
+// part is plain C++ that a host compiler also accepts (frame_plan.hpp,
+// slice_walk.hpp and their host tests use it).
 #pragma once
 #include <cstdint>
 
@@ -81,6 +82,22 @@ __device__ __forceinline__ uint32_t wave_add(uint32_t v) {
   v = row_add16(v);
   return (uint32_t)__builtin_amdgcn_readlane((int)v, 0) + (uint32_t)__builtin_amdgcn_readlane((int)v, 16) +
          (uint32_t)__builtin_amdgcn_readlane((int)v, 32) + (uint32_t)__builtin_amdgcn_readlane((int)v, 48);
+}
+// Among the wave's lanes with q set: those below this lane, and all of them (wave-uniform).
+__device__ __forceinline__ void wave_rank(bool q, uint32_t& below, uint32_t& count) {
+  const uint64_t m = __builtin_amdgcn_ballot_w64(q);
+  below = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+  count = (uint32_t)__builtin_popcountll(m);
+}
+// An inclusive prefix sum over the wave's lanes.
+__device__ __forceinline__ uint32_t wave_scan_add(uint32_t v) {
+  const uint32_t lane = threadIdx.x & 63u;
+#pragma unroll
+  for (uint32_t d = 1; d < 64; d <<= 1) {
+    const uint32_t o = (uint32_t)__shfl_up((int)v, d, 64);
+    v += lane >= d ? o : 0u;
+  }
+  return v;
 }
 
 // A value every lane holds alike, moved to scalar registers so that the

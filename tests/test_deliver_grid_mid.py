@@ -36,7 +36,7 @@ FULL = L.RxPorts.make(tcp=R.TCP_FULL, udp=R.UDP_FULL)
 
 
 def grid(n):
-    """deliver_kernel.hip grp_grid, restated."""
+    """slice_walk.hpp slice_grid under deliver_kernel.hip's kGrpBlock / kGrpGridCap, restated."""
     return min(max(-(-n // CHUNK), 1), GRID_CAP)
 
 
@@ -192,7 +192,7 @@ RING_CAP = 512
 @pytest.mark.parametrize("route", ["slots_direct", "packed"])
 def test_through_the_ring(cuda, short_pool, route):
     """lnx_rx_ring_ingress_deliver over 2 x 4352 + 300 slots: the ring sizes a stage's workspace for 4352 frames and
-    puts the keys behind grp_grid(n) histograms, so the last batch (G = 2) lays the same workspace out differently
+    puts the keys behind slice_grid(n) histograms, so the last batch (G = 2) lays the same workspace out differently
     from the two full ones (G = 17).  Frames short in their slots are read in place (zero copy) or packed on the
     host; the route is told by the counters."""
     from tests.test_rx_ring import _expect

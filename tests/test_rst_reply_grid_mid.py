@@ -33,12 +33,12 @@ POOL = 509                # short_pool's frames (a prime: no period shared with 
 
 
 def grid(n):
-    """reply_kernel.hip rp_grid, restated."""
+    """slice_walk.hpp slice_grid under reply_kernel.hip's kRpBlock / kRpGridCap, restated."""
     return min(max(-(-n // CHUNK), 1), GRID_CAP)
 
 
 def per(n):
-    """rp_slice: the chunks of a workgroup's slice."""
+    """slice_walk.hpp slice_bounds: the chunks of a workgroup's slice."""
     return -(-(-(-n // CHUNK)) // grid(n))
 
 

@@ -1,5 +1,6 @@
-"""Do two builds of crc32_kernel.hip hold the same crc32_rows_kernel machine code?
-  same_kernels.py OLD.s NEW.s     (the gfx950 .s files of two `hipcc --save-temps` runs)
+"""Do two builds of a kernel file hold the same machine code for the kernels a pattern names?
+  same_kernels.py OLD.s NEW.s [PATTERN]   (the gfx950 .s files of two `hipcc --save-temps` runs)
+PATTERN: a regular expression over the mangled kernel symbols; without one, crc32_kernel.hip's crc32_rows_kernel.
 Per kernel: the text from its label to its last s_endpgm (.Lfunc_end) without comments, with symbol
 names and the function number of .LBB<n>_<m> labels replaced, hashed, plus its
 register, scratch and LDS sizes.  The two multisets must be equal: a refactor
@@ -10,7 +11,7 @@ import hashlib
 import re
 import sys
 
-SYM = r"_ZN3lnx17crc32_rows_kernel\w+"
+SYM = sys.argv[3] if len(sys.argv) > 3 else r"_ZN3lnx17crc32_rows_kernel\w+"
 COUNTS = ("vgpr_count", "sgpr_count", "private_segment_fixed_size", "group_segment_fixed_size")
 
 
