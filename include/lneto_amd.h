@@ -702,6 +702,84 @@ int lnx_rx_echo_reply_batch(const uint8_t* d_bytes, const uint64_t* d_off, uint6
                             uint64_t cap, uint64_t cap_blocks, uint8_t* d_reply, uint64_t* d_start,
                             uint32_t* d_len, uint32_t* d_src, uint32_t* d_n, void* d_ws, void* stream);
 
+/* ARP: the third frame the stack sends back on its own, and
+ * the one no IPv4 stack works without.  arp.Handler for IPv4 over Ethernet
+ * (HardwareType 1, ProtocolType 0x0800, a 6-byte HardwareAddr, a 4-byte
+ * ProtocolAddr), registered on StackEthernet at frame offset 0.  A frame reaches
+ * it when its delivery record has verdict 0 and a handler LNX_H_ETH ..
+ * LNX_H_ETH + 8, len >= 14 and its EtherType is 0x0806.  Handler.Demux
+ * (arp/handler.go:160-203) on b = frame[14:len], P = len - 14: P < 28 gives 18
+ * (NewFrame, arp/frame.go:17-22); with minLen = 8 + 2 (b[4] + b[5]), P < minLen
+ * gives 18 and else minLen > 255 gives 2 (ValidateSize, arp/frame.go:137-146);
+ * a hardware type other than 1 / length other than 6, or a protocol type other
+ * than 0x0800 / length other than 4, gives 10; op 1 whose target b[24:28] is
+ * cfg->ip4 queues a reply entry {hw = b[8:14], ip = b[14:18]}, the sender (any
+ * sender: 0.0.0.0, a broadcast or multicast hardware address), op 1 for another
+ * address does nothing, op 2 yields a learn record (the sender again; the
+ * cache.Lookup that follows is host state), any other op gives 9.  An entry
+ * becomes the 42 bytes Handler.Encapsulate, entry.put and
+ * StackEthernet.Encapsulate write (handler.go:126-158, cache.go:32-71,
+ * internet/stack-ethernet.go:170-217), padded to 60 bytes, with LNX_TX_FCS its LE
+ * FCS behind them: destination = the entry's hw (trySetEthernetDst overwrites
+ * the gateway MAC with the ARP body's target hardware address), source = our
+ * MAC, 0x0806, 00 01 08 00 06 04 00 02, our MAC, our address, the entry's hw,
+ * the entry's ip.  A query (StartQuery, op 1): destination ff:ff:ff:ff:ff:ff,
+ * bytes 20-21 = 00 01, the entry's hw (zero from StartQuery) at 32-37 as it is.
+ * lnx_rst_cfg is the stack's side here too: mac is both the Ethernet source and
+ * the ARP sender (the reference configures the two separately; a working stack
+ * keeps them equal), gw_mac is not used.  The handler configured for IPv6, the
+ * cache's size, eviction and ageing, cache.Lookup and the resolve callback are
+ * NOT restated: the batch entry answers every queueing frame and emits every
+ * learn record, in arrival order, up to the caller's capacities, reports what
+ * it left out, and the host applies the learn records in order. */
+typedef struct lnx_arp_entry { uint8_t hw[6]; uint16_t zero; uint8_t ip[4]; } lnx_arp_entry;       /* 12 bytes */
+typedef struct lnx_arp_seen  { uint8_t hw[6]; uint16_t zero; uint8_t ip[4]; uint32_t src; } lnx_arp_seen; /* 16 bytes */
+/* frame[0 : len] (FCS stripped) under its record: returns 0 nothing (*out
+ * untouched), 1 a request for cfg->ip4 (*out = the sender), 2 an ARP reply
+ * (*out = the sender); *verdict (may be NULL) = Handler.Demux's error number,
+ * 0 when the frame never reaches the handler.  LNX_EINVAL for a NULL rec, out
+ * or cfg or a NULL frame with len > 0.  Only len bounds what is read. */
+int lnx_rx_arp_entry(const uint8_t* frame, size_t len, const lnx_rx_delivery* rec, const lnx_rst_cfg* cfg,
+                     lnx_arp_entry* out, uint8_t* verdict);
+/* The frame of one entry, op 1 (query) or 2 (reply): all 64 bytes of out are
+ * written (60..63 zero without LNX_TX_FCS), *len = 64 with LNX_TX_FCS, else 60.
+ * LNX_EINVAL for a NULL pointer, an op other than 1 or 2 or an unknown bit in
+ * cfg->flags. */
+int lnx_arp_frame(const lnx_rst_cfg* cfg, uint16_t op, const lnx_arp_entry* e, uint8_t out[64], uint32_t* len);
+/* A batch, chained behind lnx_rx_deliver_batch / lnx_rx_verify_deliver_batch on
+ * the same d_off (any order; an end below its start is an empty frame) and
+ * d_rec.  flags: LNX_RX_NO_FCS or 0 (frames carry their FCS).  Reply k answers
+ * the k-th request for cfg->ip4 in index order, lies in the 64-byte slot
+ * d_reply + 64 k (the frame's length is 64 with LNX_TX_FCS in cfg->flags, else
+ * 60) and d_src[k] is the index of the frame it answers; d_seen[j] is the
+ * learn record of the j-th ARP reply in index order, src its frame index, zero
+ * 0.  d_n[0..3] = {replies written = min(wanted, cap), replies wanted, seen
+ * written = min(wanted, cap_seen), seen wanted}; slots and d_src entries at or
+ * past d_n[0] and d_seen entries at or past d_n[2] are not touched.  d_seen may
+ * be NULL only with cap_seen == 0 (d_n[2] is 0, d_n[3] still reported).  d_ws:
+ * lnx_rx_arp_ws_bytes(n) bytes of the caller's device memory.  Three launches
+ * (count, a one-workgroup scan of two sums, build), none waiting for another
+ * workgroup and no global atomics: every output is a pure function of the
+ * inputs.  n == 0: LNX_OK with d_n zeroed (a NULL d_n: nothing to do); both
+ * caps 0: d_n alone is written.  Alignment: d_reply 64 bytes; d_rec and d_seen
+ * 16 (each is one 16-byte access); d_src, d_n and d_ws 4.  LNX_EINVAL: n >=
+ * 2^32, a NULL pointer with work to do, an unknown flag bit on either flags
+ * word, a pointer that is not so aligned (NULL counts as aligned).
+ * Asynchronous on `stream`; retains nothing, never synchronises the device and
+ * uses none of the library's per-stream scratch. */
+uint64_t lnx_rx_arp_ws_bytes(uint64_t n);
+int lnx_rx_arp_batch(const uint8_t* d_bytes, const uint64_t* d_off, uint64_t n, uint32_t flags,
+                     const lnx_rx_delivery* d_rec, const lnx_rst_cfg* cfg, uint64_t cap, uint64_t cap_seen,
+                     uint8_t* d_reply, uint32_t* d_src, lnx_arp_seen* d_seen, uint32_t* d_n,
+                     void* d_ws, void* stream);
+/* The same frames from explicit entries, the host's pending queries and
+ * replies: frame k = lnx_arp_frame(cfg, d_op[k], d_entry[k]) in the slot
+ * d_reply + 64 k (64-byte aligned; d_entry 4, d_op 2).  On the device an op
+ * other than 1 or 2 writes an all-zero slot (there is no per-entry status).
+ * n == 0: LNX_OK. */
+int lnx_arp_frames_batch(const lnx_rst_cfg* cfg, const lnx_arp_entry* d_entry, const uint16_t* d_op, uint64_t n,
+                         uint8_t* d_reply, void* stream);
+
 /* pcap's checksum re-verification over a batch: d_status[i] =
  * lnx_pcap_checksums(d_bytes[d_off[i] : d_off[i+1]]) for every Ethernet frame
  * (FCS stripped; an end offset below its start is an empty frame).  Four

@@ -403,6 +403,43 @@ inline int RSTFramesBatch(const RSTConfig& cfg, const tcp::RSTEntry* d_entry, ui
 }
 }  // namespace internet
 
+namespace arp {
+// arp.Handler for IPv4 over Ethernet: what Demux does with a
+// frame and what Encapsulate makes of a cache entry.  The cache itself, its
+// eviction and ageing, and CacheLookup are not mirrored: the batch forms answer
+// every request for our address and emit every reply's sender, in order.
+// internet::RSTConfig is the stack's side here too (MAC stands for
+// HandlerConfig.HardwareAddr as well; GatewayMAC is not used).
+using Entry = lnx_arp_entry;  // a hardware address and its protocol address
+using Seen = lnx_arp_seen;    // ... and the index of the frame that carried them
+constexpr uint16_t OpRequest = 1, OpReply = 2;
+// Handler.Demux for one frame under its record: 0 nothing, OpRequest a request for cfg.Addr4 (*out = the
+// sender, to be answered), OpReply a reply (*out = the sender, to be learned); *verdict: Demux's error number
+inline int EntryOf(lneto::Bytes frame, const lnx_rx_delivery& rec, const internet::RSTConfig& cfg, Entry* out,
+                   uint8_t* verdict = nullptr) {
+  const lnx_rst_cfg c = cfg.ToC();
+  return lnx_rx_arp_entry(frame.p, frame.n, &rec, &c, out, verdict);
+}
+// Handler.Encapsulate inside StackEthernet.Encapsulate for one entry: the frame's length, 0 on an argument error
+inline uint32_t Frame(const internet::RSTConfig& cfg, uint16_t op, const Entry& e, uint8_t out[64]) {
+  const lnx_rst_cfg c = cfg.ToC();
+  uint32_t n = 0;
+  return lnx_arp_frame(&c, op, &e, out, &n) == LNX_OK ? n : 0u;
+}
+inline int Batch(const uint8_t* d_frames, const uint64_t* d_off, uint64_t n, const lnx_rx_delivery* d_rec,
+                 const internet::RSTConfig& cfg, uint64_t cap, uint64_t capSeen, uint8_t* d_reply, uint32_t* d_src,
+                 Seen* d_seen, uint32_t* d_n, void* d_ws, bool noFCS = false, void* stream = nullptr) {
+  const lnx_rst_cfg c = cfg.ToC();
+  return lnx_rx_arp_batch(d_frames, d_off, n, noFCS ? LNX_RX_NO_FCS : 0u, d_rec, &c, cap, capSeen, d_reply, d_src, d_seen, d_n,
+                          d_ws, stream);
+}
+inline int FramesBatch(const internet::RSTConfig& cfg, const Entry* d_entry, const uint16_t* d_op, uint64_t n,
+                       uint8_t* d_reply, void* stream = nullptr) {
+  const lnx_rst_cfg c = cfg.ToC();
+  return lnx_arp_frames_batch(&c, d_entry, d_op, n, d_reply, stream);
+}
+}  // namespace arp
+
 namespace netdev {
 // Receive ring: bufferSelect-style pinned slots
 // (x/netdev/buffer.go:25-37) whose batches run through FCS verify and the

@@ -30,6 +30,8 @@ __all__ = [
     "RstCfg", "TcpRst", "TX_FCS", "TCP_RST", "TCP_ACK", "ip4_id_chain", "rx_rst_entry", "tcp_rst_frame",
     "rx_rst_ws_bytes", "rx_rst_reply_batch", "tcp_rst_frames_batch",
     "IcmpEcho", "rx_echo_entry", "icmp_echo_reply_frame", "rx_echo_ws_bytes", "rx_echo_reply_batch",
+    "ArpEntry", "ARP_SEEN_DTYPE", "ARP_REQUEST", "ARP_REPLY", "rx_arp_entry", "arp_frame", "rx_arp_ws_bytes",
+    "rx_arp_batch", "arp_frames_batch",
 ]
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -179,7 +181,29 @@ class IcmpEcho(ctypes.Structure):
         return e
 
 
+class ArpEntry(ctypes.Structure):
+    """lnx_arp_entry (include/lneto_amd.h): a hardware address and the protocol
+    address it belongs to — the sender of an ARP frame, or what the cache's
+    entry.put writes into the target fields (arp/cache.go:65-67)."""
+    _fields_ = [("hw", ctypes.c_uint8 * 6), ("zero", ctypes.c_uint16), ("ip", ctypes.c_uint8 * 4)]
+
+    @classmethod
+    def make(cls, hw: bytes, ip: bytes) -> "ArpEntry":
+        if len(hw) != 6 or len(ip) != 4:
+            raise LnetoError("ArpEntry: hw 6 bytes, ip 4")
+        e = cls()
+        e.hw[:] = list(hw)
+        e.ip[:] = list(ip)
+        return e
+
+
 _sig = {
+    "lnx_rx_arp_entry": (ctypes.c_int, [_vp, ctypes.c_size_t, _vp, _vp, _vp, _vp]),
+    "lnx_arp_frame": (ctypes.c_int, [_vp, ctypes.c_uint16, _vp, _vp, _vp]),
+    "lnx_rx_arp_ws_bytes": (ctypes.c_uint64, [ctypes.c_uint64]),
+    "lnx_rx_arp_batch": (ctypes.c_int, [_vp, _vp, ctypes.c_uint64, ctypes.c_uint32, _vp, _vp, ctypes.c_uint64,
+                                        ctypes.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lnx_arp_frames_batch": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_uint64, _vp, _vp]),
     "lnx_rx_echo_entry": (ctypes.c_int, [_vp, ctypes.c_size_t, _vp, _vp]),
     "lnx_icmp_echo_reply_frame": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_uint16, _vp, ctypes.c_uint32, _vp]),
     "lnx_rx_echo_ws_bytes": (ctypes.c_uint64, [ctypes.c_uint64]),
@@ -1046,6 +1070,104 @@ def rx_echo_reply_batch(d_bytes, d_off, d_rec, cfg: RstCfg, ip_id: int | None = 
             stream.synchronize()
         counts = d_n.cpu().numpy().view("uint32")
     return reply, start, length, src, int(counts[0]), int(counts[1])
+
+
+# ------------------------------------------------------- ARP
+ARP_REQUEST, ARP_REPLY = 1, 2  # arp.OpRequest, arp.OpReply: the ops, and the kinds rx_arp_entry gives
+# lnx_arp_seen as a numpy structured dtype (16 bytes): seen.cpu().numpy().view(ARP_SEEN_DTYPE)
+try:
+    ARP_SEEN_DTYPE = _np.dtype([("hw", "u1", (6,)), ("zero", "<u2"), ("ip", "u1", (4,)), ("src", "<u4")])
+    assert ARP_SEEN_DTYPE.itemsize == 16
+except NameError:  # pragma: no cover  (no numpy)
+    ARP_SEEN_DTYPE = None
+
+
+def rx_arp_entry(frame: bytes, rec, cfg: RstCfg):
+    """What arp.Handler.Demux does with ONE frame (FCS stripped) under its delivery
+    record (lnx_rx_arp_entry): returns (kind, entry, verdict) — kind 0 nothing,
+    ARP_REQUEST a request for cfg's address, ARP_REPLY an ARP reply; entry the
+    sender as dict(hw=, ip=), None for kind 0; verdict Demux's error number (0
+    when the frame never reaches the handler).  rec: rx_deliver's dict, or the 16
+    record bytes."""
+    raw = _record_bytes("rx_arp_entry", rec)
+    buf = bytes(frame)
+    e = ArpEntry()
+    v = ctypes.c_uint8(0)
+    rc = lib.lnx_rx_arp_entry(buf, len(buf), raw, ctypes.byref(cfg), ctypes.byref(e), ctypes.byref(v))
+    if rc < 0:
+        _check(rc, "lnx_rx_arp_entry")
+    return rc, (dict(hw=bytes(e.hw), ip=bytes(e.ip)) if rc else None), v.value
+
+
+def arp_frame(cfg: RstCfg, op: int, entry) -> bytes:
+    """The frame of one entry (an ArpEntry, or a dict as rx_arp_entry gives), op
+    ARP_REQUEST (a query) or ARP_REPLY (lnx_arp_frame): 64 bytes with cfg's fcs, else 60."""
+    e = entry if isinstance(entry, ArpEntry) else ArpEntry.make(**entry)
+    out = (ctypes.c_uint8 * 64)()
+    n = ctypes.c_uint32(0)
+    _check(lib.lnx_arp_frame(ctypes.byref(cfg), op & 0xFFFF, ctypes.byref(e), out, ctypes.byref(n)), "lnx_arp_frame")
+    return bytes(out[:n.value])
+
+
+def rx_arp_ws_bytes(n: int) -> int:
+    """Bytes of device workspace lnx_rx_arp_batch needs for n frames."""
+    return lib.lnx_rx_arp_ws_bytes(n)
+
+
+def rx_arp_batch(d_bytes, d_off, d_rec, cfg: RstCfg, cap: int | None = None, cap_seen: int | None = None, flags: int = 0,
+                 stream=None):
+    """The ARP replies and learn records of a batch behind rx_deliver_batch /
+    rx_verify_deliver_batch on the same d_off and records (lnx_rx_arp_batch):
+    returns (reply, src, seen, counts).  reply is [cap, 64] uint8, reply k in row
+    k (its first 60 bytes without cfg's fcs), answering frame src[k] (int32, cap);
+    seen is [cap_seen, 16] uint8, one lnx_arp_seen a row
+    (seen.cpu().numpy().view(ARP_SEEN_DTYPE)); counts = (replies written, replies
+    wanted, seen written, seen wanted); rows at or past what was written are left
+    as allocated.  Both capacities default to the number of frames.  flags:
+    RX_NO_FCS or 0.  Synchronises to return the counts."""
+    import torch
+    what = "lnx_rx_arp_batch"
+    b = _Batch(what, [("d_bytes", d_bytes, "u8"), ("d_off", d_off, "i64"), ("d_rec", d_rec, "u8")], stream)
+    n = d_off.numel() - 1
+    if n < 0:
+        raise LnetoError(f"{what}: d_off holds no offset")
+    _need_len(what, "d_rec", d_rec, 16 * n)
+    cap = n if cap is None else int(cap)
+    cap_seen = n if cap_seen is None else int(cap_seen)
+    reply = torch.empty((cap, 64), dtype=torch.uint8, device=b.device)
+    src = torch.empty(cap, dtype=torch.int32, device=b.device)
+    seen = torch.empty((cap_seen, 16), dtype=torch.uint8, device=b.device)
+    d_n = torch.empty(4, dtype=torch.int32, device=b.device)  # (written by every call)
+    ws = torch.empty(rx_arp_ws_bytes(n), dtype=torch.uint8, device=b.device)
+    with b as s:
+        _check(lib.lnx_rx_arp_batch(d_bytes.data_ptr(), d_off.data_ptr(), n, flags, d_rec.data_ptr(), ctypes.byref(cfg),
+                                    cap, cap_seen, reply.data_ptr() if cap else None, src.data_ptr() if cap else None,
+                                    seen.data_ptr() if cap_seen else None, d_n.data_ptr(), ws.data_ptr(), s), what)
+        if stream is not None:
+            ws.record_stream(stream)
+            stream.synchronize()
+        counts = d_n.cpu().numpy().view("uint32")
+    return reply, src, seen, tuple(int(c) for c in counts)
+
+
+def arp_frames_batch(cfg: RstCfg, d_entry, d_op, out=None, stream=None):
+    """The frames of explicit entries (lnx_arp_frames_batch): d_entry is [n, 12]
+    uint8, one lnx_arp_entry a row (ArpEntry), d_op an int16 device tensor of n
+    ops (ARP_REQUEST / ARP_REPLY; any other op gives an all-zero slot); returns
+    reply [n, 64] uint8."""
+    import torch
+    what = "lnx_arp_frames_batch"
+    b = _Batch(what, [("d_entry", d_entry, "u8"), ("d_op", d_op, "i16")], stream)
+    if d_entry.numel() % 12:
+        raise LnetoError(f"{what}: d_entry holds 12 bytes an entry")
+    n = d_entry.numel() // 12
+    _need_len(what, "d_op", d_op, n)
+    reply = _out(what, out, 64 * n, torch.uint8, "u8", b.device)
+    if n > 0:
+        with b as s:
+            _check(lib.lnx_arp_frames_batch(ctypes.byref(cfg), d_entry.data_ptr(), d_op.data_ptr(), n, reply.data_ptr(), s),
+                   what)
+    return reply.view(-1)[:64 * n].view(n, 64)
 
 
 PCAP_IP_HDR_BAD, PCAP_PROTO_BAD = 1, 2  # LNX_PCAP_IP_HDR_BAD, LNX_PCAP_PROTO_BAD

@@ -739,6 +739,44 @@ int lnx_rx_echo_reply_batch(const uint8_t* d_bytes, const uint64_t* d_off, uint6
   return LNX_OK;
 }
 
+uint64_t lnx_rx_arp_ws_bytes(uint64_t n) { return lnxa::arp_ws_bytes(n); }
+
+// ARP replies and learn records behind the delivery records (arp_kernel.hip,
+// DESIGN.md §3.22).  The workspace is the caller's, as in the delivery entries;
+// the device context gives the table image only (the RST image: the frame is 60
+// bytes too).
+int lnx_rx_arp_batch(const uint8_t* d_bytes, const uint64_t* d_off, uint64_t n, uint32_t flags,
+                     const lnx_rx_delivery* d_rec, const lnx_rst_cfg* cfg, uint64_t cap, uint64_t cap_seen,
+                     uint8_t* d_reply, uint32_t* d_src, lnx_arp_seen* d_seen, uint32_t* d_n, void* d_ws, void* stream) {
+  if (!reply_args_ok(flags, cfg, n, d_reply, d_rec, d_src, d_n, d_ws, 4, nullptr)) return LNX_EINVAL;
+  if (misaligned(d_seen, 16)) return LNX_EINVAL;
+  const hipStream_t hs = static_cast<hipStream_t>(stream);
+  if (n == 0) return zero_words(d_n, 4, hs, "hipMemsetAsync(d_n)");
+  if (!d_bytes || !d_off || !d_rec || !cfg || !d_n || !d_ws) return LNX_EINVAL;
+  if ((cap > 0 && (!d_reply || !d_src)) || (cap_seen > 0 && !d_seen)) return LNX_EINVAL;
+  DeviceCtx* c = nullptr;
+  const int st = get_ctx(&c);
+  if (st != LNX_OK) return st;
+  const hipError_t e = lnxa::launch_arp_reply(d_bytes, d_off, n, (flags & LNX_RX_NO_FCS) ? 0u : 4u, d_rec, *cfg, cap, cap_seen,
+                                              d_reply, d_src, d_seen, d_n, d_ws, c->d_rst, hs);
+  if (e != hipSuccess) return hip_fail(e, "arp kernels launch");
+  return LNX_OK;
+}
+
+int lnx_arp_frames_batch(const lnx_rst_cfg* cfg, const lnx_arp_entry* d_entry, const uint16_t* d_op, uint64_t n,
+                         uint8_t* d_reply, void* stream) {
+  if (cfg && (cfg->flags & ~(uint32_t)LNX_TX_FCS)) return LNX_EINVAL;
+  if (misaligned(d_reply, 64) || misaligned(d_entry, 4) || misaligned(d_op, 2)) return LNX_EINVAL;
+  if (n == 0) return LNX_OK;
+  if (!cfg || !d_entry || !d_op || !d_reply) return LNX_EINVAL;
+  DeviceCtx* c = nullptr;
+  const int st = get_ctx(&c);
+  if (st != LNX_OK) return st;
+  const hipError_t e = lnxa::launch_arp_frames(*cfg, d_entry, d_op, n, d_reply, c->d_rst, static_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return hip_fail(e, "arp_frames_kernel launch");
+  return LNX_OK;
+}
+
 int lnx_pcap_verify_batch(const uint8_t* d_bytes, const uint64_t* d_off, uint64_t n, uint8_t* d_status,
                           void* stream) {
   if (n == 0) return LNX_OK;

@@ -65,6 +65,16 @@ hipError_t launch_echo_reply(const uint8_t* bytes, const uint64_t* off, uint64_t
                              hipStream_t stream);
 }  // namespace lnxe
 
+// arp_kernel.hip: ARP replies and learn records
+namespace lnxa {
+uint64_t arp_ws_bytes(uint64_t n);
+hipError_t launch_arp_reply(const uint8_t* bytes, const uint64_t* off, uint64_t n, uint32_t trim, const lnx_rx_delivery* rec,
+                            const lnx_rst_cfg& cfg, uint64_t cap, uint64_t cap_seen, uint8_t* reply, uint32_t* src,
+                            lnx_arp_seen* seen, uint32_t* d_n, void* ws, const uint32_t* image, hipStream_t stream);
+hipError_t launch_arp_frames(const lnx_rst_cfg& cfg, const lnx_arp_entry* entry, const uint16_t* op, uint64_t n, uint8_t* reply,
+                             const uint32_t* image, hipStream_t stream);
+}  // namespace lnxa
+
 namespace lnx {
 
 // api.cpp: the current device's images and CU count, and the thread's lnx_last_error
