@@ -3,14 +3,12 @@
 // entries (arp_kernel.hip).  Plain C++17 with no HIP in it: the library builds
 // it, and tests/cpp/arp_plan_host.cpp builds it again with g++ under
 // AddressSanitizer and UBSan, together with table_images.cpp, whose RST image
-// gives the FCS here as it does in the kernel.
+// gives the FCS here as it does in the kernel (slot_frame.hpp).
 #include <cstddef>
 #include <cstdint>
 #include <cstring>
-#include <vector>
 #include "arp_plan.hpp"
-#include "table_images.hpp"
-#include "table_layout.hpp"
+#include "host_path.hpp"
 
 namespace {
 
@@ -35,36 +33,21 @@ lnxa::ArpEntry get_entry(const lnx_arp_entry& in) {
 extern "C" int lnx_rx_arp_entry(const uint8_t* frame, size_t len, const lnx_rx_delivery* rec, const lnx_rst_cfg* cfg,
                                 lnx_arp_entry* out, uint8_t* verdict) {
   if (!rec || !out || !cfg || (len > 0 && !frame)) return LNX_EINVAL;
-  const uint32_t L = len < 0x7FFFFFFFu ? (uint32_t)len : 0x7FFFFFFFu;
-  auto byt = [&](uint32_t o) -> uint32_t { return frame[o]; };
-  auto be16 = [&](uint32_t o) -> uint32_t { return ((uint32_t)frame[o] << 8) | frame[o + 1]; };
+  const lnx::HostFrame fr(frame, len);
   if (verdict) *verdict = 0;
-  if (!lnxa::arp_reaches(L, rec->verdict, rec->handler, be16)) return 0;
+  if (!lnxa::arp_reaches(fr.L, rec->verdict, rec->handler, fr.be16())) return 0;
   uint32_t v = 0;
-  const uint32_t kind = lnxa::arp_demux(L, lnxa::arp_cfg_of(*cfg), byt, v);
+  const uint32_t kind = lnxa::arp_demux(fr.L, lnxa::arp_cfg_of(*cfg), fr.byt(), v);
   if (verdict) *verdict = (uint8_t)v;
   if (kind == lnxa::kArpNone) return 0;
-  put_entry(lnxa::arp_entry_of(byt), out);
+  put_entry(lnxa::arp_entry_of(fr.byt()), out);
   return (int)kind;
 }
 
 extern "C" int lnx_arp_frame(const lnx_rst_cfg* cfg, uint16_t op, const lnx_arp_entry* e, uint8_t out[64], uint32_t* len) {
   if (!cfg || !e || !out || !len || !lnxa::arp_op_ok(op) || (cfg->flags & ~(uint32_t)LNX_TX_FCS)) return LNX_EINVAL;
-  static const std::vector<uint32_t> image = lnx::build_rst_image();
   const lnxa::ArpCfg c = lnxa::arp_cfg_of(*cfg);
   const lnxa::ArpEntry en = get_entry(*e);
-  auto tab = [&](uint32_t p, uint32_t i, uint32_t v) -> uint32_t { return image[lnx::rst_nib(p, i, v)]; };
-  uint32_t reg = 0;
-  for (uint32_t p = 0; p < lnxa::kArpWords; ++p) {
-    uint32_t w = 0;
-    if (p < lnx::kRstLanes) {
-      w = lnxa::arp_word(p, lnxa::arp_fixed_word(p, c), en, op);
-      reg ^= lnxr::rst_fcs_part(p, w, tab);
-    } else if (c.fcs) {
-      w = ~reg;
-    }
-    for (uint32_t b = 0; b < 4; ++b) out[4 * p + b] = (uint8_t)(w >> (8 * b));  // little-endian dwords
-  }
-  *len = c.fcs ? 64u : lnxa::kArpPadded;
+  *len = lnx::slot_frame(c.fcs, out, [&](uint32_t p) -> uint32_t { return lnxa::arp_word(p, lnxa::arp_fixed_word(p, c), en, op); });
   return LNX_OK;
 }

@@ -12,28 +12,23 @@
 //   scan   over the workgroups in index order (one workgroup): the two running
 //          sums in the same rounds, and d_n;
 //   build  each workgroup walks its slice again in index order, a chunk of
-//          kArBlock frames at a time: a thread per frame decides (the front
+//          kSlotBlock frames at a time: a thread per frame decides (the front
 //          end) and is ranked once per kind by ballot / mbcnt; a kind-2 thread
 //          stores its own record; the chunk's kind-1 entries are staged in LDS
-//          by rank, and a 16-lane row per reply writes its 16 dwords as one
-//          aligned 64-byte block (the row stage of §3.19, with the FCS from the
-//          kRstImgZ tables).
+//          by rank, and the row stage of slot_frame.hpp writes a reply's 16
+//          dwords as one aligned 64-byte block.
 // lnx_arp_frames_batch is the row stage behind the other front end: the
-// caller's explicit entries and ops.
+// caller's explicit entries and ops (slot_frame.hpp slot_frames).
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include "arp_plan.hpp"
 #include "launch.hpp"
 #include "slice_walk.hpp"
-#include "table_layout.hpp"
+#include "slot_frame.hpp"
 
 namespace lnxa {
 
-// (kArBlock, kArGridCap and kArFramesGridCap are restated in tests/test_arp_reply_gpu.py)
-constexpr int kArBlock = 256;                  // frames per chunk: one per thread (tests: CHUNK)
-constexpr uint32_t kArWaves = kArBlock / 64, kArRows = kArBlock / 16;
-constexpr uint32_t kArGridCap = 512;           // workgroups of the count / build launches (tests: GRID_CAP)
-constexpr uint32_t kArFramesGridCap = 2048;    // ... of the explicit-entries launch, grid-strided past it (tests: FRAMES_GRID_CAP)
+using lnx::kSlotBlock, lnx::kSlotWaves, lnx::kSlotGridCap;
 
 // ------------------------------------------------------------------ front end: records
 // Frame bytes 14 .. 41, the ARP body, as seven little-endian dwords.  Eight
@@ -82,125 +77,91 @@ __device__ __forceinline__ uint32_t ar_kind(const uint8_t* __restrict__ bytes, c
 // ------------------------------------------------------------------ count, scan
 // ws: cnt1[G], then cnt2[G].  The count launch writes entry g of both; the scan
 // turns them into the sums before workgroup g.
-__global__ void __launch_bounds__(kArBlock)
+__global__ void __launch_bounds__(kSlotBlock)
 arp_count_kernel(const uint8_t* __restrict__ bytes, const uint64_t* __restrict__ off, uint64_t n, uint32_t trim,
                  const uint4* __restrict__ rec, ArpCfg cfg, uint32_t* __restrict__ counts) {
-  __shared__ uint32_t w1[kArWaves], w2[kArWaves];
+  __shared__ uint32_t w1[kSlotWaves], w2[kSlotWaves];
   uint64_t lo, hi;
-  lnx::slice_bounds(n, kArBlock, lo, hi);
+  lnx::slice_bounds(n, kSlotBlock, lo, hi);
   uint32_t c1 = 0, c2 = 0;
-  for (uint64_t c0 = lo; c0 < hi; c0 += kArBlock) {  // (uniform)
+  for (uint64_t c0 = lo; c0 < hi; c0 += kSlotBlock) {  // (uniform)
     const uint64_t i = c0 + threadIdx.x;
     ArpEntry e;
     const uint32_t kind = i < hi ? ar_kind(bytes, off, trim, rec, i, cfg, e) : kArpNone;
     c1 += kind == kArpRequest ? 1u : 0u;
     c2 += kind == kArpReply ? 1u : 0u;
   }
-  c1 = lnx::wave_add(c1);
-  c2 = lnx::wave_add(c2);
-  if ((threadIdx.x & 63u) == 0) w1[threadIdx.x >> 6] = c1, w2[threadIdx.x >> 6] = c2;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint32_t s1 = 0, s2 = 0;
-    for (uint32_t w = 0; w < kArWaves; ++w) s1 += w1[w], s2 += w2[w];
-    counts[blockIdx.x] = s1;
-    counts[gridDim.x + blockIdx.x] = s2;
-  }
+  lnx::ScanSlot<uint32_t> s1{w1, lnx::wave_add(c1), 0u}, s2{w2, lnx::wave_add(c2), 0u};
+  lnx::block_total<kSlotWaves>(s1, s2);
+  if (threadIdx.x == 0) counts[blockIdx.x] = s1.v, counts[gridDim.x + blockIdx.x] = s2.v;
 }
 
 // d_n = {replies written, replies wanted, seen written, seen wanted}
-__global__ void __launch_bounds__(kArGridCap)
+__global__ void __launch_bounds__(kSlotGridCap)
 arp_scan_kernel(uint32_t* __restrict__ counts, uint32_t G, uint64_t cap, uint64_t cap_seen, uint32_t* __restrict__ d_n) {
-  __shared__ uint32_t part1[kArGridCap], part2[kArGridCap];
+  __shared__ uint32_t part1[kSlotGridCap], part2[kSlotGridCap];
   const uint32_t t = threadIdx.x;
   const uint32_t c1 = t < G ? counts[t] : 0u, c2 = t < G ? counts[G + t] : 0u;
   lnx::ScanSlot<uint32_t> s1{part1, c1, 0u}, s2{part2, c2, 0u};
-  lnx::block_scan_inclusive<kArGridCap>(s1, s2);  // the two sums in the same rounds
+  lnx::block_scan_inclusive<kSlotGridCap>(s1, s2);  // the two sums in the same rounds
   if (t < G) counts[t] = s1.v - c1, counts[G + t] = s2.v - c2;
   if (t == G - 1u) {  // the last workgroup's inclusive sums: the totals (n < 2^32)
-    d_n[0] = s1.v < cap ? s1.v : (uint32_t)cap;
-    d_n[1] = s1.v;
-    d_n[2] = s2.v < cap_seen ? s2.v : (uint32_t)cap_seen;
-    d_n[3] = s2.v;
+    lnx::written_wanted(d_n, s1.v, cap);
+    lnx::written_wanted(d_n + 2, s2.v, cap_seen);
   }
 }
 
-// ------------------------------------------------------------------ the row stage
+// ------------------------------------------------------------------ the row stage's entries
 // A chunk's entries in LDS, by rank: the entry's three dwords, the op in the upper half of the second.
 struct ArStage {
-  uint32_t d0[kArBlock], d1[kArBlock], d2[kArBlock];
+  uint32_t d0[kSlotBlock], d1[kSlotBlock], d2[kSlotBlock];
 };
 
-// Replies k0 .. k0 + m - 1 from the staged entries 0 .. m - 1: row `row` takes
-// entries row, row + 16, ...; lane p of the row makes dword p (arp_plan.hpp
-// arp_word), the row XORs the fifteen shares of the FCS and lane 15 holds its
-// complement.  The row's sixteen stores are one whole aligned 64-byte block.
-// An op other than 1 or 2 (explicit entries only): sixteen zero dwords.
-template <bool FCS>
-__device__ __forceinline__ void ar_rows(const ArStage& st, const uint32_t* tab, uint32_t m, uint64_t k0, const ArpCfg& cfg,
-                                        uint32_t* __restrict__ reply) {
-  const uint32_t p = threadIdx.x & 15u, row = threadIdx.x >> 4;
-  const uint32_t pw = p < lnx::kRstLanes ? p : lnx::kRstLanes - 1u;
-  const uint32_t fixed = arp_fixed_word(pw, cfg);
-  for (uint32_t j0 = 0; j0 < m; j0 += kArRows) {  // (uniform: m <= kArBlock, so j < kArBlock; a row past m stores nothing)
-    const uint32_t j = j0 + row;
+// slot_rows' callable: dword pw of staged entry j (arp_plan.hpp arp_word).  An op
+// other than 1 or 2 (explicit entries only) clears `live`: sixteen zero dwords.
+// The lane's fixed word is made here, once.
+__device__ __forceinline__ auto ar_word(const ArStage& st, const ArpCfg& cfg) {
+  const uint32_t fixed = arp_fixed_word(lnx::slot_lane_word(), cfg);
+  return [&st, fixed](uint32_t pw, uint32_t j, bool& live) -> uint32_t {
     ArpEntry e;
     e.d0 = st.d0[j], e.d1 = st.d1[j] & 0xFFFFu, e.d2 = st.d2[j];
     const uint32_t op = st.d1[j] >> 16;
-    uint32_t w = arp_word(pw, fixed, e, op);
-    if (FCS) {
-      uint32_t z = lnxr::rst_fcs_part(pw, w, [tab](uint32_t q, uint32_t i, uint32_t v) -> uint32_t { return tab[lnx::rst_nib(q, i, v)]; });
-      z = lnx::row_xor16(p < lnx::kRstLanes ? z : 0u);
-      w = p < lnx::kRstLanes ? w : ~z;
-    } else {
-      w = p < lnx::kRstLanes ? w : 0u;
-    }
-    if (j < m) reply[(k0 + j) * kArpWords + p] = arp_op_ok(op) ? w : 0u;
-  }
-}
-
-__device__ __forceinline__ void ar_tables(uint32_t* tab, const uint32_t* __restrict__ image) {
-  for (uint32_t i = threadIdx.x; i < lnx::kRstImageDwords; i += kArBlock) tab[i] = image[lnx::kRstImgZ + i];
+    live = arp_op_ok(op);
+    return arp_word(pw, fixed, e, op);
+  };
 }
 
 // ------------------------------------------------------------------ build
 // run1, run2: the frames of kind 1 and of kind 2 before the chunk (the scan's
 // bases of this workgroup, then the chunks walked).  A frame's rank in its chunk,
-// once per kind: the waves' counts before its wave (through LDS) plus the lanes
-// of that kind below it in its wave.  Nothing at or past `cap` (slots, d_src)
+// once per kind: slice_walk.hpp chunk_rank.  Nothing at or past `cap` (slots, d_src)
 // or `cap_seen` (d_seen) is written; seen may be NULL with cap_seen 0.
 template <bool FCS>
-__global__ void __launch_bounds__(kArBlock)
+__global__ void __launch_bounds__(kSlotBlock)
 arp_build_kernel(const uint8_t* __restrict__ bytes, const uint64_t* __restrict__ off, uint64_t n, uint32_t trim,
                  const uint4* __restrict__ rec, ArpCfg cfg, uint64_t cap, uint64_t cap_seen,
                  const uint32_t* __restrict__ base, const uint32_t* __restrict__ image, uint32_t* __restrict__ reply,
                  uint32_t* __restrict__ src, uint4* __restrict__ seen) {
   __shared__ uint32_t tab[FCS ? lnx::kRstImageDwords : 1];
   __shared__ ArStage st;
-  __shared__ uint32_t wc1[kArWaves], wc2[kArWaves];
-  const uint32_t t = threadIdx.x, wave = t >> 6;
+  __shared__ uint32_t wc1[kSlotWaves], wc2[kSlotWaves];
+  const uint32_t t = threadIdx.x;
   uint64_t run1 = base[blockIdx.x], run2 = base[gridDim.x + blockIdx.x];
   if (run1 >= cap && run2 >= cap_seen) return;  // (uniform) both boundaries lie before this slice
-  if (FCS) ar_tables(tab, image);
+  if (FCS) lnx::slot_tables(tab, image);
+  const auto word = ar_word(st, cfg);
   uint64_t lo, hi;
-  lnx::slice_bounds(n, kArBlock, lo, hi);
-  for (uint64_t c0 = lo; c0 < hi && (run1 < cap || run2 < cap_seen); c0 += kArBlock) {  // (uniform: every wave keeps all its lanes)
+  lnx::slice_bounds(n, kSlotBlock, lo, hi);
+  for (uint64_t c0 = lo; c0 < hi && (run1 < cap || run2 < cap_seen); c0 += kSlotBlock) {  // (uniform: every wave keeps all its lanes)
     const uint64_t i = c0 + t;
     ArpEntry e;
     const uint32_t kind = i < hi ? ar_kind(bytes, off, trim, rec, i, cfg, e) : kArpNone;
-    uint32_t below1, n1, below2, n2;
-    lnx::wave_rank(kind == kArpRequest, below1, n1);
-    lnx::wave_rank(kind == kArpReply, below2, n2);
-    __syncthreads();  // the last chunk's rows are done with st and the counts (and, first, the tables' stores)
-    if ((t & 63u) == 0) wc1[wave] = n1, wc2[wave] = n2;
-    __syncthreads();
-    uint32_t before1, total1, before2, total2;
-    lnx::waves_before<kArWaves>(wc1, wave, before1, total1);
-    lnx::waves_before<kArWaves>(wc2, wave, before2, total2);
-    const uint64_t k1 = run1 + before1 + below1, k2 = run2 + before2 + below2;
-    if (kind == kArpReply && k2 < cap_seen) seen[k2] = make_uint4(e.d0, e.d1, e.d2, (uint32_t)i);  // lnx_arp_seen
-    if (kind == kArpRequest && k1 < cap) {
-      const uint32_t r = before1 + below1;  // < kArBlock
+    lnx::RankSlot q1{wc1, kind == kArpRequest, 0u, 0u}, q2{wc2, kind == kArpReply, 0u, 0u};
+    lnx::chunk_rank<kSlotWaves>(q1, q2);  // (its first barrier: the last chunk's rows are done with st, and, first, the tables' stores)
+    const uint64_t k1 = run1 + q1.rank, k2 = run2 + q2.rank;
+    if (q2.q && k2 < cap_seen) seen[k2] = make_uint4(e.d0, e.d1, e.d2, (uint32_t)i);  // lnx_arp_seen
+    if (q1.q && k1 < cap) {
+      const uint32_t r = q1.rank;  // < kSlotBlock
       st.d0[r] = e.d0;
       st.d1[r] = e.d1 | (kArpReply << 16);
       st.d2[r] = e.d2;
@@ -208,78 +169,61 @@ arp_build_kernel(const uint8_t* __restrict__ bytes, const uint64_t* __restrict__
     }
     __syncthreads();
     const uint64_t room = run1 < cap ? cap - run1 : 0u;
-    ar_rows<FCS>(st, tab, total1 < room ? total1 : (uint32_t)room, run1, cfg, reply);
-    run1 += total1;
-    run2 += total2;
+    lnx::slot_rows<FCS>(tab, q1.total < room ? q1.total : (uint32_t)room, run1, reply, word);
+    run1 += q1.total;
+    run2 += q2.total;
   }
 }
 
 // ------------------------------------------------------------------ front end: explicit entries
 // entry: lnx_arp_entry as three little-endian dwords; reply k from entry k and op k.
+struct ArFrames {
+  using Stage = ArStage;
+  const uint32_t* __restrict__ entry;
+  const uint16_t* __restrict__ op;
+  const ArpCfg& cfg;
+  __device__ __forceinline__ void load(Stage& st, uint32_t t, uint64_t i) const {
+    const uint32_t* w = entry + 3u * i;
+    st.d0[t] = w[0];
+    st.d1[t] = (w[1] & 0xFFFFu) | ((uint32_t)op[i] << 16);
+    st.d2[t] = w[2];
+  }
+  __device__ __forceinline__ auto word(const Stage& st) const { return ar_word(st, cfg); }
+};
 template <bool FCS>
-__global__ void __launch_bounds__(kArBlock)
+__global__ void __launch_bounds__(kSlotBlock)
 arp_frames_kernel(const uint32_t* __restrict__ entry, const uint16_t* __restrict__ op, uint64_t n, ArpCfg cfg,
                   const uint32_t* __restrict__ image, uint32_t* __restrict__ reply) {
-  __shared__ uint32_t tab[FCS ? lnx::kRstImageDwords : 1];
-  __shared__ ArStage st;
-  const uint32_t t = threadIdx.x;
-  if (FCS) ar_tables(tab, image);
-  for (uint64_t c0 = (uint64_t)blockIdx.x * kArBlock; c0 < n; c0 += (uint64_t)gridDim.x * kArBlock) {  // (uniform)
-    const uint64_t i = c0 + t;
-    __syncthreads();  // the last chunk's rows are done with st (and, first, the tables' stores)
-    if (i < n) {
-      const uint32_t* w = entry + 3u * i;
-      st.d0[t] = w[0];
-      st.d1[t] = (w[1] & 0xFFFFu) | ((uint32_t)op[i] << 16);
-      st.d2[t] = w[2];
-    }
-    __syncthreads();
-    const uint64_t left = n - c0;
-    ar_rows<FCS>(st, tab, left < (uint64_t)kArBlock ? (uint32_t)left : (uint32_t)kArBlock, c0, cfg, reply);
-  }
+  lnx::slot_frames<FCS>(ArFrames{entry, op, cfg}, n, image, reply);
 }
 
 // ------------------------------------------------------------------ launchers
 // ws: the workgroups' kind-1 counts, then bases (G words), and the same of kind 2 (G words)
-uint64_t arp_ws_bytes(uint64_t n) { return (uint64_t)lnx::slice_grid(n, kArBlock, kArGridCap) * 8u; }
+uint64_t arp_ws_bytes(uint64_t n) { return (uint64_t)lnx::slice_grid(n, kSlotBlock, kSlotGridCap) * 8u; }
 
 // n > 0.  cap == 0 and cap_seen == 0: d_n alone is written (count and scan).
 hipError_t launch_arp_reply(const uint8_t* bytes, const uint64_t* off, uint64_t n, uint32_t trim, const lnx_rx_delivery* rec,
                             const lnx_rst_cfg& cfg, uint64_t cap, uint64_t cap_seen, uint8_t* reply, uint32_t* src,
                             lnx_arp_seen* seen, uint32_t* d_n, void* ws, const uint32_t* image, hipStream_t stream) {
-  const uint32_t G = lnx::slice_grid(n, kArBlock, kArGridCap);
+  const uint32_t G = lnx::slice_grid(n, kSlotBlock, kSlotGridCap);
   const ArpCfg c = arp_cfg_of(cfg);
   const uint4* rb = reinterpret_cast<const uint4*>(rec);
   uint32_t* counts = static_cast<uint32_t*>(ws);
   hipError_t e;
-  hipLaunchKernelGGL(arp_count_kernel, dim3(G), dim3(kArBlock), 0, stream, bytes, off, n, trim, rb, c, counts);
+  hipLaunchKernelGGL(arp_count_kernel, dim3(G), dim3(kSlotBlock), 0, stream, bytes, off, n, trim, rb, c, counts);
   if ((e = hipGetLastError()) != hipSuccess) return e;
-  hipLaunchKernelGGL(arp_scan_kernel, dim3(1), dim3(kArGridCap), 0, stream, counts, G, cap, cap_seen, d_n);
+  hipLaunchKernelGGL(arp_scan_kernel, dim3(1), dim3(kSlotGridCap), 0, stream, counts, G, cap, cap_seen, d_n);
   if ((e = hipGetLastError()) != hipSuccess || (cap == 0 && cap_seen == 0)) return e;
-  uint32_t* out = reinterpret_cast<uint32_t*>(reply);
-  uint4* sn = reinterpret_cast<uint4*>(seen);
-  if (c.fcs)
-    hipLaunchKernelGGL(arp_build_kernel<true>, dim3(G), dim3(kArBlock), 0, stream, bytes, off, n, trim, rb, c, cap, cap_seen,
-                       counts, image, out, src, sn);
-  else
-    hipLaunchKernelGGL(arp_build_kernel<false>, dim3(G), dim3(kArBlock), 0, stream, bytes, off, n, trim, rb, c, cap, cap_seen,
-                       counts, image, out, src, sn);
-  return hipGetLastError();
+  return lnx::launch_fcs(c.fcs, arp_build_kernel<true>, arp_build_kernel<false>, dim3(G), dim3(kSlotBlock), stream, bytes, off, n,
+                         trim, rb, c, cap, cap_seen, counts, image, reinterpret_cast<uint32_t*>(reply), src,
+                         reinterpret_cast<uint4*>(seen));
 }
 
 hipError_t launch_arp_frames(const lnx_rst_cfg& cfg, const lnx_arp_entry* entry, const uint16_t* op, uint64_t n, uint8_t* reply,
                              const uint32_t* image, hipStream_t stream) {
-  if (n == 0) return hipSuccess;
   const ArpCfg c = arp_cfg_of(cfg);
-  const uint64_t chunks = (n + kArBlock - 1) / kArBlock;
-  const dim3 grid((unsigned)(chunks < kArFramesGridCap ? chunks : kArFramesGridCap));
-  const uint32_t* in = reinterpret_cast<const uint32_t*>(entry);
-  uint32_t* out = reinterpret_cast<uint32_t*>(reply);
-  if (c.fcs)
-    hipLaunchKernelGGL(arp_frames_kernel<true>, grid, dim3(kArBlock), 0, stream, in, op, n, c, image, out);
-  else
-    hipLaunchKernelGGL(arp_frames_kernel<false>, grid, dim3(kArBlock), 0, stream, in, op, n, c, image, out);
-  return hipGetLastError();
+  return lnx::launch_slot_frames(c.fcs, arp_frames_kernel<true>, arp_frames_kernel<false>, n, stream,
+                                 reinterpret_cast<const uint32_t*>(entry), op, n, c, image, reinterpret_cast<uint32_t*>(reply));
 }
 
 }  // namespace lnxa

@@ -67,7 +67,7 @@
 #pragma once
 #include <cstdint>
 #include "../../include/lneto_amd.h"
-#include "reply_plan.hpp"
+#include "slot_frame.hpp"
 #include "wave_util.hpp"
 
 namespace lnxa {
@@ -75,7 +75,6 @@ namespace lnxa {
 constexpr uint32_t kArpNone = 0, kArpRequest = 1, kArpReply = 2;  // a frame's kind; the two ops (arp/definitions.go)
 constexpr uint32_t kErrDrop = 2, kErrUnsupported = 9, kErrMismatch = 10, kErrTruncated = 18;  // errors.go
 constexpr uint32_t kEtherArp = 0x0806, kArpBody = 14, kArpV4 = 28, kArpMinL = kArpBody + kArpV4;
-constexpr uint32_t kArpWords = lnxr::kRstWords, kArpPadded = lnxr::kRstPadded;
 
 // the stack's side, as the bytes lie in memory: mac[0..1], mac[2..5] and ip4 as little-endian words
 struct ArpCfg {
@@ -156,7 +155,6 @@ LNX_HD uint32_t arp_var_word(uint32_t p, const ArpEntry& e, uint32_t op) {
 // fixed = arp_fixed_word(p, cfg)
 LNX_HD uint32_t arp_word(uint32_t p, uint32_t fixed, const ArpEntry& e, uint32_t op) { return fixed | arp_var_word(p, e, op); }
 
-// The FCS of the 60 bytes is reply_plan.hpp's: lnxr::rst_fcs_part over the
-// same kRstImgZ tables, the fifteen shares XORed and complemented.
+// The frame in its slot and its FCS: slot_frame.hpp, over the kRstImgZ tables.
 
 }  // namespace lnxa

@@ -13,17 +13,12 @@ namespace lnx {
 
 int host_echo_entry(const uint8_t* frame, size_t len, const lnx_rx_delivery* rec, lnx_icmp_echo* out) {
   if (!rec || !out || (len > 0 && !frame)) return LNX_EINVAL;
-  const uint32_t L = len < 0x7FFFFFFFu ? (uint32_t)len : 0x7FFFFFFFu;
-  auto byt = [&](uint32_t o) -> uint32_t { return frame[o]; };
-  auto be16 = [&](uint32_t o) -> uint32_t { return ((uint32_t)frame[o] << 8) | frame[o + 1]; };
-  auto be32 = [&](uint32_t o) -> uint32_t {
-    return ((uint32_t)frame[o] << 24) | ((uint32_t)frame[o + 1] << 16) | ((uint32_t)frame[o + 2] << 8) | frame[o + 3];
-  };
-  if (!lnxe::echo_queues(L, rec->verdict, rec->handler, rec->l4_off, rec->ip_end, byt)) return 0;
-  const lnxe::EchoEntry e = lnxe::echo_entry_of(rec->l4_off, rec->ip_end, be16, be32);
+  const HostFrame fr(frame, len);
+  if (!lnxe::echo_queues(fr.L, rec->verdict, rec->handler, rec->l4_off, rec->ip_end, fr.byt())) return 0;
+  const lnxe::EchoEntry e = lnxe::echo_entry_of(rec->l4_off, rec->ip_end, fr.be16(), fr.be32());
   static_assert(sizeof(lnx_icmp_echo) == 16, "include/lneto_amd.h");
   lnx_icmp_echo r;
-  for (uint32_t i = 0; i < 4; ++i) r.remote_addr[i] = (uint8_t)(e.addr >> (24 - 8 * i));
+  put_addr_be(e.addr, r.remote_addr);
   r.id = (uint16_t)e.id, r.seq = (uint16_t)e.seq;
   r.data_off = e.data_off, r.data_len = e.data_len;
   *out = r;
@@ -39,8 +34,7 @@ int host_echo_reply_frame(const lnx_rst_cfg* cfg, const lnx_icmp_echo* e, const 
   const lnxe::RstCfg c = lnxr::rst_cfg_of(*cfg);
   const uint32_t padded = lnxe::echo_padded(d), total = lnxe::echo_len(d, c.fcs);
   if (out_cap < total) return 6;
-  const uint32_t addr = ((uint32_t)e->remote_addr[0] << 24) | ((uint32_t)e->remote_addr[1] << 16) |
-                        ((uint32_t)e->remote_addr[2] << 8) | e->remote_addr[3];
+  const uint32_t addr = addr_be(e->remote_addr);
   uint32_t be_sum = (uint32_t)e->id + e->seq;  // type 0, code 0 and the zeroed checksum field add nothing
   for (uint32_t k = 0; k + 1 < d; k += 2) be_sum += ((uint32_t)data[k] << 8) | data[k + 1];
   if (d & 1u) be_sum += (uint32_t)data[d - 1] << 8;

@@ -30,6 +30,7 @@
 #include "echo_plan.hpp"
 #include "launch.hpp"
 #include "slice_walk.hpp"
+#include "slot_frame.hpp"
 #include "table_layout.hpp"
 
 namespace lnxe {
@@ -87,15 +88,10 @@ echo_count_kernel(const uint8_t* __restrict__ bytes, const uint64_t* __restrict_
     c += lnx::wave_add(q ? 1u : 0u);
     b += lnx::wave_add(q ? echo_blocks(end - l4 - 8u, fcs) : 0u);  // (a chunk's blocks fit 32 bits)
   }
-  if ((threadIdx.x & 63u) == 0) wcnt[threadIdx.x >> 6] = c, wblk[threadIdx.x >> 6] = b;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint32_t sc = 0;
-    uint64_t sb = 0;
-    for (uint32_t w = 0; w < kEpWaves; ++w) sc += wcnt[w], sb += wblk[w];
-    ep_ws_cnt(ws, gridDim.x)[blockIdx.x] = sc;
-    ep_ws_blk(ws)[blockIdx.x] = sb;
-  }
+  lnx::ScanSlot<uint32_t> sc{wcnt, c, 0u};
+  lnx::ScanSlot<uint64_t> sb{wblk, b, 0u};
+  lnx::block_total<kEpWaves>(sc, sb);
+  if (threadIdx.x == 0) ep_ws_cnt(ws, gridDim.x)[blockIdx.x] = sc.v, ep_ws_blk(ws)[blockIdx.x] = sb.v;
 }
 
 // d_n = {written, wanted, blocks written, blocks wanted}.  When the totals exceed a
@@ -391,14 +387,8 @@ hipError_t launch_echo_reply(const uint8_t* bytes, const uint64_t* off, uint64_t
   if ((e = hipGetLastError()) != hipSuccess) return e;
   hipLaunchKernelGGL(echo_scan_kernel, dim3(1), dim3(kEpGridCap), 0, stream, ws, G, cap, cap_blocks, d_n);
   if ((e = hipGetLastError()) != hipSuccess || cap == 0 || cap_blocks == 0) return e;
-  uint32_t* out = reinterpret_cast<uint32_t*>(reply);
-  if (c.fcs)
-    hipLaunchKernelGGL(echo_reply_kernel<true>, dim3(G), dim3(kEpBlock), 0, stream, bytes, off, n, trim, rb, c, ip_id, cap,
-                       cap_blocks, ws, image, out, start, len, src, d_n);
-  else
-    hipLaunchKernelGGL(echo_reply_kernel<false>, dim3(G), dim3(kEpBlock), 0, stream, bytes, off, n, trim, rb, c, ip_id, cap,
-                       cap_blocks, ws, image, out, start, len, src, d_n);
-  return hipGetLastError();
+  return lnx::launch_fcs(c.fcs, echo_reply_kernel<true>, echo_reply_kernel<false>, dim3(G), dim3(kEpBlock), stream, bytes, off, n,
+                         trim, rb, c, ip_id, cap, cap_blocks, ws, image, reinterpret_cast<uint32_t*>(reply), start, len, src, d_n);
 }
 
 }  // namespace lnxe

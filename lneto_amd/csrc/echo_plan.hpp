@@ -71,6 +71,7 @@
 #include <cstdint>
 #include "../../include/lneto_amd.h"
 #include "reply_plan.hpp"
+#include "slot_frame.hpp"
 #include "wave_util.hpp"
 
 namespace lnxe {
@@ -139,10 +140,10 @@ LNX_HD uint32_t echo_var_field(uint32_t k, uint32_t addr, uint32_t id, uint32_t 
   return k == 8 ? 28u + d : k == 9 ? (ip_id & 0xFFFFu) : k == 12 ? ip_sum : k == 15 ? (addr >> 16) : k == 16 ? (addr & 0xFFFFu)
        : k == 18 ? icmp_sum : k == 19 ? (id & 0xFFFFu) : 0u;
 }
-LNX_HD uint32_t echo_fixed_word(uint32_t p, const RstCfg& c) { return lnxr::rst_pack(echo_fixed_field(2 * p, c), echo_fixed_field(2 * p + 1, c)); }
+LNX_HD uint32_t echo_fixed_word(uint32_t p, const RstCfg& c) { return lnx::slot_pack(echo_fixed_field(2 * p, c), echo_fixed_field(2 * p + 1, c)); }
 // dword p < 10 of the frame as it lies in memory: fixed = echo_fixed_word(p, cfg)
 LNX_HD uint32_t echo_word(uint32_t p, uint32_t fixed, uint32_t addr, uint32_t id, uint32_t d, uint32_t ip_id, uint32_t ip_sum, uint32_t icmp_sum) {
-  return fixed | lnxr::rst_pack(echo_var_field(2 * p, addr, id, d, ip_id, ip_sum, icmp_sum),
+  return fixed | lnx::slot_pack(echo_var_field(2 * p, addr, id, d, ip_id, ip_sum, icmp_sum),
                                 echo_var_field(2 * p + 1, addr, id, d, ip_id, ip_sum, icmp_sum));
 }
 

@@ -61,13 +61,13 @@
 #pragma once
 #include <cstdint>
 #include "../../include/lneto_amd.h"
+#include "slot_frame.hpp"
 #include "wave_util.hpp"
 
 namespace lnxr {
 
 constexpr uint32_t kDlvRst = LNX_DLV_RST;
 constexpr uint32_t kTcpRst = 0x04u, kTcpAck = 0x10u, kTcpFlagMask = 0x1FFu;  // tcp/definitions.go:158-168
-constexpr uint32_t kRstWords = 16, kRstFields = 30, kRstPadded = 60;
 
 // the stack's side of a reply: 16-bit big-endian fields
 struct RstCfg {
@@ -145,27 +145,13 @@ LNX_HD uint32_t rst_var_field(uint32_t k, const RstEntry& e, uint32_t id, uint32
        : k == 21 ? (e.ack >> 16) : k == 22 ? (e.ack & 0xFFFFu) : k == 23 ? (0x5000u | (e.flags & kTcpFlagMask))
        : k == 25 ? tcp_sum : 0u;
 }
-// two fields as the little-endian dword that holds them in memory
-LNX_HD uint32_t rst_pack(uint32_t f0, uint32_t f1) {
-  return ((f0 >> 8) & 0xFFu) | ((f0 & 0xFFu) << 8) | (((f1 >> 8) & 0xFFu) << 16) | ((f1 & 0xFFu) << 24);
-}
-LNX_HD uint32_t rst_fixed_word(uint32_t p, const RstCfg& c) { return rst_pack(rst_fixed_field(2 * p, c), rst_fixed_field(2 * p + 1, c)); }
-// dword p < 15 of the frame: fixed = rst_fixed_word(p, cfg)
+// dword p < 15 of the frame as it lies in memory (slot_frame.hpp slot_pack): the first part ...
+LNX_HD uint32_t rst_fixed_word(uint32_t p, const RstCfg& c) { return lnx::slot_pack(rst_fixed_field(2 * p, c), rst_fixed_field(2 * p + 1, c)); }
+// ... and the whole: fixed = rst_fixed_word(p, cfg)
 LNX_HD uint32_t rst_word(uint32_t p, uint32_t fixed, const RstEntry& e, uint32_t id, uint32_t ip_sum, uint32_t tcp_sum) {
-  return fixed | rst_pack(rst_var_field(2 * p, e, id, ip_sum, tcp_sum), rst_var_field(2 * p + 1, e, id, ip_sum, tcp_sum));
+  return fixed | lnx::slot_pack(rst_var_field(2 * p, e, id, ip_sum, tcp_sum), rst_var_field(2 * p + 1, e, id, ip_sum, tcp_sum));
 }
 
-// The FCS of the 60 bytes.  Processing a dword w at register r is Z_4(r ^ w)
-// (gf2.hpp), so the register after the fifteen dwords is
-//   XOR_p Z_{4 (15 - p)}(w_p)  ^  Z_60(0xFFFFFFFF),
-// the init folded into dword 0, and the CRC its complement.  tab(p, i, v): entry
-// v of nibble table i of Z_{4 (15 - p)} (table_layout.hpp kRstImgZ).
-template <class Tab>
-LNX_HD uint32_t rst_fcs_part(uint32_t p, uint32_t word, Tab tab) {
-  const uint32_t w = p == 0 ? ~word : word;
-  uint32_t z = 0;
-  for (uint32_t i = 0; i < 8; ++i) z ^= tab(p, i, (w >> (4 * i)) & 15u);
-  return z;
-}
+// The frame in its slot and its FCS: slot_frame.hpp, over the kRstImgZ tables.
 
 }  // namespace lnxr

@@ -2,8 +2,10 @@
 // and the reply kernels: G workgroups, each owning ONE
 // contiguous index slice of whole chunks; a first launch counts per slice, one
 // workgroup scans the counts in index order, and a last launch walks the same
-// slices again, a chunk at a time, ranking each frame in its chunk.  The first
-// part is plain C++ that a host compiler also accepts (tests/cpp/slice_walk_host.cpp).
+// slices again, a chunk at a time, ranking each frame in its chunk
+// (block_total, written_wanted and chunk_rank: the three launches' shared
+// steps).  The first part is plain C++ that a host compiler also accepts
+// (tests/cpp/slice_walk_host.cpp).
 #pragma once
 #include <cstdint>
 #include "wave_util.hpp"
@@ -31,6 +33,11 @@ LNX_HD uint32_t frame_len(uint64_t s, uint64_t e, uint32_t trim) {
   const uint64_t lt = e > s ? e - s : 0;  // an end below its start: an empty frame
   const uint32_t Lt = lt < 0x7FFFFFFFull ? (uint32_t)lt : 0x7FFFFFFFu;
   return Lt > trim ? Lt - trim : 0u;
+}
+// What a scan launch reports of one sum: d_n[0] = the entries written, the first `cap` of them, d_n[1] = all of them.
+LNX_HD void written_wanted(uint32_t* d_n, uint32_t total, uint64_t cap) {
+  d_n[0] = total < cap ? total : (uint32_t)cap;
+  d_n[1] = total;
 }
 
 #if defined(__HIPCC__)
@@ -87,6 +94,44 @@ __device__ __forceinline__ T block_scan_inclusive(T* lds, T v) {  // one sum
   ScanSlot<T> s{lds, v, T{}};
   block_scan_inclusive<N>(s);
   return s.v;
+}
+
+// The count launches' tail.  v: the wave's sum, in every lane of it; lds: an
+// array of kWaves per sum.  Thread 0 leaves with the workgroup's sum in v (the
+// other threads' v is not a sum).  One barrier; every thread of the workgroup calls it.
+template <uint32_t kWaves, typename... T>
+__device__ __forceinline__ void block_total(ScanSlot<T>&... s) {
+  if ((threadIdx.x & 63u) == 0) ((s.lds[threadIdx.x >> 6] = s.v), ...);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    ((s.v = T{}), ...);
+    for (uint32_t w = 0; w < kWaves; ++w) ((s.v += s.lds[w]), ...);
+  }
+}
+
+// A thread's rank in its chunk among the threads with q set, and the chunk's
+// count of them: the waves' counts before its wave (through LDS, an array of
+// kWaves per sum) plus the set lanes below it in its wave.  Two barriers,
+// shared by all the sums of one call: the first also ends the last chunk's
+// reads of whatever the caller stages by rank.  Every thread of the workgroup calls it.
+struct RankSlot {
+  uint32_t* lds;
+  bool q;
+  uint32_t rank, total;
+};
+template <uint32_t kWaves, typename... S>
+__device__ __forceinline__ void chunk_rank(S&... s) {
+  const uint32_t wave = threadIdx.x >> 6;
+  (wave_rank(s.q, s.rank, s.total), ...);
+  __syncthreads();
+  if ((threadIdx.x & 63u) == 0) ((s.lds[wave] = s.total), ...);
+  __syncthreads();
+  auto join = [wave](RankSlot& r) {
+    uint32_t before;
+    waves_before<kWaves>(r.lds, wave, before, r.total);
+    r.rank += before;
+  };
+  (join(s), ...);
 }
 #endif  // __HIPCC__
 

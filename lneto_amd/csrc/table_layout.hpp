@@ -64,7 +64,7 @@ constexpr uint32_t kOctLevOff = kOctNibOff + kBankCols * kNib8Dwords;   // Z_{19
 constexpr uint32_t kOctTabDwords = kOctLevOff + 3 * kByte4Dwords - kOctNibOff;  // (copied in one piece)
 constexpr uint32_t kSearchTableDwords = kOctNibOff + kOctTabDwords;
 
-// ---- the RST reply image (reply_kernel.hip, reply_host.cpp: reply_plan.hpp rst_fcs_part)
+// ---- the RST reply image, of any 60-byte frame in a 64-byte slot (slot_frame.hpp slot_fcs_part: RST and ARP replies)
 constexpr uint32_t kRstLanes = 15;                                      // the dwords of a 60-byte frame
 constexpr uint32_t kRstImgZ = 0;                                        // Z_{4(15-p)} nibble tables, p < 15: dword p's share of the FCS
 constexpr uint32_t kRstImageDwords = kRstImgZ + kRstLanes * kNib8Dwords;

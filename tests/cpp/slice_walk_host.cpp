@@ -1,5 +1,5 @@
 // slice_walk_host.cpp — the host-compilable part of lneto_amd/csrc/slice_walk.hpp
-// (slice_grid, slice_bounds, frame_len), compiled stand-alone for
+// (slice_grid, slice_bounds, frame_len, written_wanted), compiled stand-alone for
 // tests/test_slice_walk_host.py: no GPU.  Built a second time with
 // AddressSanitizer and UBSan; nothing but this program is loaded.
 //
@@ -57,6 +57,15 @@ int main() {
   CHECK(lnx::frame_len(5, ~0ull, 4) == 0x7FFFFFFBu && lnx::frame_len(0, 0x7FFFFFFEull, 0) == 0x7FFFFFFEu);
   CHECK(lnx::frame_len(10, 13, 4) == 0 && lnx::frame_len(10, 14, 4) == 0 && lnx::frame_len(10, 15, 4) == 1);
   CHECK(lnx::frame_len(0, 1, 0xFFFFFFFFu) == 0);
+  // written_wanted: the first `cap` of the total are written, all of it is wanted; a cap above 2^32 changes nothing
+  const struct { uint32_t total; uint64_t cap; uint32_t written; } ww[] = {
+      {0, 0, 0}, {7, 0, 0}, {7, 6, 6}, {7, 7, 7}, {7, 8, 7}, {0xFFFFFFFFu, 0xFFFFFFFEull, 0xFFFFFFFEu},
+      {0xFFFFFFFFu, 0x100000000ull, 0xFFFFFFFFu}, {5, ~0ull, 5}};
+  for (const auto& c : ww) {
+    uint32_t d_n[4] = {0xA5A5A5A5u, 0xA5A5A5A5u, 0xA5A5A5A5u, 0xA5A5A5A5u};
+    lnx::written_wanted(d_n + 1, c.total, c.cap);
+    CHECK(d_n[0] == 0xA5A5A5A5u && d_n[1] == c.written && d_n[2] == c.total && d_n[3] == 0xA5A5A5A5u);
+  }
   printf(g_fail ? "FAILED %d\n" : "frame_len: ok\n", g_fail);
   return g_fail ? 1 : 0;
 }

@@ -19,8 +19,8 @@ from tests.test_deliver_gpu import FILT, dev, host_records, packed, with_fcs
 
 pytestmark = pytest.mark.gpu
 
-CHUNK, GRID_CAP = 256, 512       # arp_kernel.hip: kArBlock frames a chunk, kArGridCap workgroups
-FRAMES_GRID_CAP = 2048           # ... kArFramesGridCap workgroups of the explicit-entries launch
+CHUNK, GRID_CAP = 256, 512       # slot_frame.hpp: kSlotBlock frames a chunk, kSlotGridCap workgroups
+FRAMES_GRID_CAP = 2048           # ... kSlotFramesGridCap workgroups of the explicit-entries launch
 CFG = {fcs: L.RstCfg.make(mac=A.MAC, gw_mac=A.GW_MAC, ip4=A.IP4, fcs=fcs) for fcs in (False, True)}
 FILL = 0xA5
 PAD = 8                          # sentinel rows behind each capacity

@@ -16,7 +16,7 @@ from tests.test_deliver_gpu import DUP, FILT, dev, host_records, packed, with_fc
 
 pytestmark = pytest.mark.gpu
 
-CHUNK, GRID_CAP = 256, 512       # reply_kernel.hip: kRpBlock frames a chunk, kRpGridCap workgroups
+CHUNK, GRID_CAP = 256, 512       # slot_frame.hpp: kSlotBlock frames a chunk, kSlotGridCap workgroups
 CFG = {fcs: L.RstCfg.make(mac=R.MAC, gw_mac=R.GW_MAC, ip4=R.IP4, fcs=fcs) for fcs in (False, True)}
 FILL = 0xA5
 PAD = 8                          # sentinel rows behind the capacity
@@ -218,8 +218,9 @@ def test_stale_records(cuda, pool):
 
 
 # ------------------------------------------------------------ explicit entries
-@pytest.mark.parametrize("n", [1, 64, 1000])
+@pytest.mark.parametrize("n", [1, 15, 16, 17, 64, 256, 257, 1000])
 def test_explicit_entries(cuda, n):
+    """Around a row of 16 and a chunk of 256 (the stage is slot_frame.hpp's, as ARP's is), with the FCS and without."""
     import torch
     rng = np.random.default_rng(n)
     raw = rng.integers(0, 256, (n, 20), dtype=np.uint8)

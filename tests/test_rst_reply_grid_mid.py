@@ -26,14 +26,14 @@ from tests.test_rst_reply_gpu import CFG, chain, check, cycled, expected, forced
 
 pytestmark = pytest.mark.gpu
 
-CHUNK = 256               # reply_kernel.hip kRpBlock: frames per chunk
-GRID_CAP = 512            # reply_kernel.hip kRpGridCap: workgroups of the count / build launches
-FRAMES_GRID_CAP = 2048    # reply_kernel.hip kRpFramesGridCap: workgroups of the explicit-entries launch
+CHUNK = 256               # slot_frame.hpp kSlotBlock: frames per chunk
+GRID_CAP = 512            # slot_frame.hpp kSlotGridCap: workgroups of the count / build launches
+FRAMES_GRID_CAP = 2048    # slot_frame.hpp kSlotFramesGridCap: workgroups of the explicit-entries launch
 POOL = 509                # short_pool's frames (a prime: no period shared with the chunks)
 
 
 def grid(n):
-    """slice_walk.hpp slice_grid under reply_kernel.hip's kRpBlock / kRpGridCap, restated."""
+    """slice_walk.hpp slice_grid under slot_frame.hpp's kSlotBlock / kSlotGridCap, restated."""
     return min(max(-(-n // CHUNK), 1), GRID_CAP)
 
 
