@@ -6,6 +6,9 @@ its frames' mean length, so a given test batch exercises only some of the
 compiled configurations.  The profiling entry point lnx__crc32_variant forces
 one configuration for the whole launch (ids in lneto_amd/csrc/research/crc_variants.inc,
 each a product configuration of rows_cfg.hpp with some fields changed).
+This covers the research build's forced widths in CRC mode only; the product
+instance on lengths its dispatch sample does not see (CRC, FCS verify, running
+CRCs) is pinned by tests/test_rows_hidden_lengths.py.
 """
 import ctypes
 
